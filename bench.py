@@ -78,7 +78,17 @@ def parse_args(argv=None):
                          "(configs[4]'s per-rank output, overlapInCore.C:197)")
     ap.add_argument("--no-side", action="store_true",
                     help="skip the side lines (configs[4] rank job, MHAP configs[3]) that the "
-                         "default 1-GPU run adds after the headline")
+                         "--full 1-GPU run adds after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beside the headline: the "
+                         "record parity check, the live probe ceilings of the roofline, the "
+                         "seed-only and per-shard figures, the shared-index timing (N > 1), the "
+                         "CPU baseline and the side lines (each still has its --no-* switch); "
+                         "without it the run sets up, warms up, times the steps and prints")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write the last timed step's output as "
+                         "DIR/<name>.npy (float64): records.npy, the ovOverlap records in "
+                         "ovStore order, and counters.npy, the job's -s counters")
     a = ap.parse_args(argv)
     c4 = a.workload == "configs4-rank"
     if a.reads is None:
@@ -164,35 +174,13 @@ def main() -> None:
     gbp = job.total_bases / 1e9
     gbp_vs_gbp = gbp * gbp / 2.0 * args.steps / elapsed    # all-vs-all, each pair once
 
-    # ---- parity of the last step's records against the reference's digest ------------
-    parity = None
-    if not args.no_parity:
-        parity = job.parity(st, reduce, SUM, torch)
+    # --dump-outputs: the last timed step's records and counters, for build-to-build compares
+    dumped = dump_outputs(args.dump_outputs, oic, st, rank, world) if args.dump_outputs else None
 
-    roof, probe_roof, traffic_note = rooflines(args, job, st, world)
-    ovb = job.write_output(args.ovb_out) if args.ovb_out else None
-
-    seed_only = job.seed_only() if world == 1 and not args.no_seed_only else None
-    shard = job.shard_timing(ms_step) if world == 1 and not args.no_shard_timing else None
-    xgmi = None
-    # over RCCL; on the one-GPU rehearsal (CANU_DEVICE, gloo) too, for the path's logic
-    if world > 1 and (backend == "nccl" or "CANU_DEVICE" in os.environ):
-        try:
-            xgmi = job.index_allgather_timing(torch)
-        except Exception as e:          # a side measurement: never lose the bench line to it
-            xgmi = {"error": f"{type(e).__name__}: {e}"[:300]}
-
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "configs2":
-        cpu = cpu_baseline(args)
-
-    side = None
-    if rank == 0 and world == 1 and args.workload == "configs2" and not args.no_side:
-        # the GPU is handed to the side runs: this job's buffers are released first
-        oic.close()
-        job.release()
-        torch.cuda.empty_cache()
-        side = side_runs()
+    x = after_timing(args, job, st, rank, world, backend, ms_step, reduce, SUM, torch)
+    parity, ovb, side = x["parity"], x["ovb"], x["side"]
+    roof, probe_roof, traffic_note = x["rooflines"]
+    seed_only, shard, xgmi, cpu = x["seed_only"], x["shard_timing"], x["xgmi"], x["cpu"]
 
     if rank == 0:
         line = {
@@ -228,12 +216,56 @@ def main() -> None:
         }
         if ovb is not None:
             line["ovb_output"] = ovb
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if side is not None:
             line.update(side)
         print(json.dumps(line), flush=True)
     oic.close()
     if dist:
         dist.destroy_process_group()
+
+
+def after_timing(args, job, st, rank, world, backend, ms_step, reduce, SUM, torch) -> dict:
+    """What the line carries beside the headline.  A plain run only does the roofline
+    arithmetic over the last step's own stats (and --ovb-out when asked); everything that
+    takes a run of its own -- parity, the live probe ceilings, seed-only, shard timing, the
+    shared-index timing, the CPU baseline, the side lines -- needs --full and is None
+    without it."""
+    full = args.full
+    # ---- parity of the last step's records against the reference's digest ------------
+    parity = None
+    if full and not args.no_parity:
+        parity = job.parity(st, reduce, SUM, torch)
+
+    roofs = rooflines(args, job, st, world, live=full)
+    ovb = job.write_output(args.ovb_out) if args.ovb_out else None
+
+    seed_only = job.seed_only() if full and world == 1 and not args.no_seed_only else None
+    shard = job.shard_timing(ms_step) if full and world == 1 and not args.no_shard_timing \
+        else None
+    xgmi = None
+    # over RCCL; on the one-GPU rehearsal (CANU_DEVICE, gloo) too, for the path's logic
+    if full and world > 1 and (backend == "nccl" or "CANU_DEVICE" in os.environ):
+        try:
+            xgmi = job.index_allgather_timing(torch)
+        except Exception as e:          # a side measurement: never lose the bench line to it
+            xgmi = {"error": f"{type(e).__name__}: {e}"[:300]}
+
+    cpu = None
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline and \
+            args.workload == "configs2":
+        cpu = cpu_baseline(args)
+
+    side = None
+    if full and rank == 0 and world == 1 and args.workload == "configs2" and not args.no_side:
+        # the GPU is handed to the side runs: this job's buffers are released first
+        job.oic.close()
+        job.release()
+        torch.cuda.empty_cache()
+        side = side_runs()
+    return {"parity": parity, "rooflines": roofs, "ovb": ovb, "seed_only": seed_only,
+            "shard_timing": shard, "xgmi": xgmi, "cpu": cpu, "side": side}
 
 
 class Configs2:
@@ -674,9 +706,45 @@ def load_traffic(job, world: int):
     return t, f"profiles/{fname} ({meta.get('tag')}, same workload and sources)"
 
 
-def rooflines(args, job, st, world):
+DUMP_MAX_BYTES = 60_000_000     # of the 64 MB a dump may hold
+DUMP_COUNTERS = ("total_overlaps", "kmer_hits_with_olap", "kmer_hits_without_olap",
+                 "kmer_hits_skipped", "multi_overlaps", "contained_overlaps",
+                 "dovetail_overlaps", "seed_hits", "seed_nodes", "pairs")
+
+
+def dump_outputs(out_dir: str, oic, st, rank: int, world: int) -> dict:
+    """--dump-outputs: what the last timed step handed back, as float64 .npy files that two
+    builds can be compared by.  records.npy: the ovOverlap records in ovStore order (the
+    order they leave the GPU in is not fixed), one row per record = a_iid, b_iid and the two
+    packed 64-bit dat words as four 32-bit halves (low half first), every value exact in a
+    double; above DUMP_MAX_BYTES a fixed seeded sample of the sorted rows, drawn before the
+    rows are widened.  The sampled positions depend on the record count, so the samples of
+    two outputs that differ in size share few rows: equal outputs give equal files, unequal
+    ones show first in counters.npy.  counters.npy: the job's counters in DUMP_COUNTERS
+    order, then the number of records.  At N > 1 every rank writes its own shard's files
+    (<name>_rankNN.npy)."""
+    from canu_amd import digest
+    os.makedirs(out_dir, exist_ok=True)
+    rec = digest.sort_records(oic.fetch())
+    n = int(rec.shape[0])
+    max_rows = DUMP_MAX_BYTES // (6 * 8)
+    if n > max_rows:
+        rec = rec[np.sort(np.random.default_rng(0).choice(n, size=max_rows, replace=False))]
+    m = int(rec.shape[0])
+    rows = np.empty((m, 6), dtype=np.float64)
+    rows[:, 0], rows[:, 1] = rec["a"], rec["b"]
+    rows[:, 2:] = np.stack([rec["w0"], rec["w1"]], axis=1).view("<u4").reshape(m, 4)
+    counters = np.array([float(st[k]) for k in DUMP_COUNTERS] + [float(n)], dtype=np.float64)
+    suffix = "" if world == 1 else f"_rank{rank:02d}"
+    np.save(os.path.join(out_dir, f"records{suffix}.npy"), rows)
+    np.save(os.path.join(out_dir, f"counters{suffix}.npy"), counters)
+    return {"records": n, "rows_written": int(rows.shape[0])}
+
+
+def rooflines(args, job, st, world, live=True):
     """The dominant kernel (k_extend) against the roofline that binds it -- instruction
-    issue -- with its HBM figures beside; and the hash-probe kernel against HBM."""
+    issue -- with its HBM figures beside; and the hash-probe kernel against HBM.  live=False
+    leaves out the ceilings that are measured by kernel runs of their own."""
     traffic, note = load_traffic(job, world)
     n = job.n
     avg_len = job.total_bases / max(job.nloaded, 1)
@@ -760,6 +828,9 @@ def rooflines(args, job, st, world):
         if tb:
             probe_roof["traffic_gbs"] = round(tb / (avg_ms * 1e-3) / 1e9, 1)
             probe_roof["traffic_frac"] = round(probe_roof["traffic_gbs"] / HBM_PEAK_GBS, 4)
+        if not live:
+            probe_roof["random_lookup_ceiling"] = None
+            return roof, probe_roof, note
         wps = achieved * 1e9 / PROBE_BYTES_PER_WINDOW
         # the ceiling of one random lookup per window, measured now on this device over this
         # run's own index table (ovl_probe_ceiling: 8 independent random 16-B loads in flight
@@ -791,7 +862,7 @@ def rooflines(args, job, st, world):
 def side_runs(timeout_s: int = 300) -> dict:
     """The other two workloads BASELINE.json names, each timed by its own bench in a child
     process on this GPU after the headline (one warm-up + one timed job each), so the
-    driver's default run records them too; the headline's value is not touched:
+    driver's --full run records them too; the headline's value is not touched:
       configs4_rank  bench.py --workload configs4-rank (one rank job of configs[4]'s 8-GPU
                      plan at 1/8 scale, with its PMC-keyed issue roofline when
                      profiles/traffic_configs4.json matches these sources)
@@ -804,7 +875,7 @@ def side_runs(timeout_s: int = 300) -> dict:
     keep3 = ("value", "unit", "ms_per_step", "breakdown_ms", "config", "setup_s", "roofline",
              "candidates_per_step", "overlaps_per_step", "parity")
     runs = {"configs4_rank": ([sys.executable, os.path.join(ROOT, "bench.py"), "--workload",
-                               "configs4-rank", "--steps", "1", "--warmup", "1",
+                               "configs4-rank", "--steps", "1", "--warmup", "1", "--full",
                                "--no-cpu-baseline", "--no-side"], keep4),
             "mhap_configs3": ([sys.executable, os.path.join(ROOT, "bench_mhap.py"), "--steps",
                                "1", "--warmup", "1", "--no-cpu-baseline"], keep3)}

@@ -13,9 +13,9 @@ sys.path.insert(0, ROOT)
 def test_overlapincore_traffic_matches_sources_and_workloads(monkeypatch):
     import bench
     monkeypatch.delenv("CANU_C4_PLAN", raising=False)
-    # the default line and the configs4-rank side line exactly as bench.py runs them
-    for argv, cls in ((["--steps", "1"], bench.Configs2),
-                      (["--workload", "configs4-rank", "--steps", "1", "--warmup", "1",
+    # the --full line and its configs4-rank side line exactly as bench.py runs them
+    for argv, cls in ((["--steps", "1", "--full"], bench.Configs2),
+                      (["--workload", "configs4-rank", "--steps", "1", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-side"], bench.Configs4Rank)):
         job = cls(bench.parse_args(argv), 0, 1, None)
         traffic, note = bench.load_traffic(job, 1)
