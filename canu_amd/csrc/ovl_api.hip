@@ -1831,7 +1831,10 @@ static int find_impl(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, ui
     return c->h_error_bound[std::min<uint64_t>(L, AS_MAX_READLEN)] + 2;
   };
   auto sw_of = [](uint64_t L) { return (int32_t)(((L + 31) / 32 + 2) & ~1ull); };
-  auto stg_lds_of = [&](uint64_t L) { return 4ull * (4ull * (uint64_t)sw_of(L) + OVL_SCR_STAGE); };
+  // per wave: the two strands' plane words, the scratch and the pair-state block
+  auto stg_lds_of = [&](uint64_t L) {
+    return 4ull * (4ull * (uint64_t)sw_of(L) + OVL_SCR_STAGE + OVL_STATE_INTS);
+  };
   auto ml_of = [](int32_t ec) { return 4ull * (((uint64_t)(ec + 2) + 3) & ~3ull); };
   // the staged kernel's block-shared Edit_Match_Limit table
   auto sml_of = [&](int32_t ec) { return ml_of(ec); };
@@ -1936,9 +1939,9 @@ static int find_impl(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, ui
   gen.ecap = ecap_of(c->max_len);
   {
     const size_t ml = ml_of(gen.ecap);
-    size_t w = 4ull * ((2ull * (2 * gen.ecap + 8) + TB_ROWS * TB_W + OVL_LDCAP + 3) & ~3ull);
+    size_t w = 4ull * ((2ull * (2 * gen.ecap + 8) + TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3ull);
     gen.l16 = w + ml > 160 * 1024;                       // GR
-    if (gen.l16) w = 4ull * ((TB_ROWS * TB_W + OVL_LDCAP + 3) & ~3ull);
+    if (gen.l16) w = 4ull * ((TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3ull);
     gen.wpb = (4 * w <= 80 * 1024) ? 4 : (2 * w <= 80 * 1024) ? 2 : 1;
     gen.lds = w * gen.wpb + (gen.l16 ? 0 : ml);
     uint64_t st = (uint64_t)(gen.ecap + 2) * (gen.ecap + 2) + 4ull * (gen.ecap + 2) + 64;

@@ -111,6 +111,7 @@ struct WaveMem {
   int32_t  ldcap;
   const lds_i32 *mlim;  // LDS: Edit_Match_Limit[0 .. e_cap+1], shared by the block
   ml_t    *rmlim;       // the register kernel's Edit_Match_Limit (the LDS copy)
+  lds_i32 *state;       // LDS: the wave's pair state (OVL_STATE_INTS, below)
 };
 
 __device__ __forceinline__ void lds_sync() {
@@ -671,9 +672,32 @@ __device__ __forceinline__ double uni(double v) {
   return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
+// A record loaded with a wave-uniform index, every field as a scalar.
+__device__ __forceinline__ PairRec uni_rec(const PairRec &p) {
+  PairRec r;
+  r.unit = (uint32_t)uni((int32_t)p.unit); r.tgt = (uint32_t)uni((int32_t)p.tgt);
+  r.node_off = (uint32_t)uni((int32_t)p.node_off); r.node_cnt = (uint32_t)uni((int32_t)p.node_cnt);
+  r.diag_ct = uni(p.diag_ct); r.diag_bgn = uni(p.diag_bgn); r.diag_end = uni(p.diag_end);
+  r.flags = (uint32_t)uni((int32_t)p.flags);
+  return r;
+}
+__device__ __forceinline__ Unit uni_rec(const Unit &u) {
+  Unit r;
+  r.r = (uint32_t)uni((int32_t)u.r); r.dir = (uint32_t)uni((int32_t)u.dir);
+  return r;
+}
+__device__ __forceinline__ Strand uni_strand(const Strand &s) {
+  Strand r;
+  r.w = uni_ptr(s.w); r.ex_wild = uni_ptr(s.ex_wild); r.ex_nul = uni_ptr(s.ex_nul);
+  r.len = uni(s.len);
+  return r;
+}
+
 // The row loop stays a call: inlined into process_pair (always_inline) the kernel keeps 80
 // VGPRs but spills 576 B per lane inside the loop -- extension 218 -> 297 ms (+37 %) on the
-// 10k-read job (r02v A/B).
+// 10k-read job (r02v A/B).  With the caller's state scalar or in LDS (round 7) the inlined
+// kernel needs 52 B of scratch per lane, 12 VGPR spills, none in the row loops, and measures
+// the same as the call (211.2 vs 209.7 ms, profiles/r07a_ab.txt): the call, half the code.
 #ifndef OVL_PED_ATTR
 #define OVL_PED_ATTR noinline
 #endif
@@ -1106,6 +1130,44 @@ struct OlapInfo {
   int32_t min_diag, max_diag;
 };
 
+// The wave's pair state in LDS: what has to survive the row-loop calls but is only read
+// between them -- the nine 64-bit output counters and the pair's (up to three) distinct
+// overlaps.  In registers these were 18 + 42 VGPRs (or, indexed, a scratch array) that the
+// caller spilled around every call; here lane 0 writes a value and every lane reads it back
+// as a scalar.
+#define OVL_STATE_INTS 64
+#define OVL_ST_OL 18              // ints 0..17: the counters; then 3 x 14 ints of OlapInfo
+#define OVL_OL_INTS 14
+static_assert(sizeof(OlapInfo) == 4 * OVL_OL_INTS, "OlapInfo's LDS image");
+static_assert(OVL_ST_OL + 3 * OVL_OL_INTS <= OVL_STATE_INTS, "the state block holds them");
+typedef __attribute__((address_space(3))) double lds_f64;
+
+__device__ __forceinline__ void st_inc(lds_i32 *state, int i, uint32_t lane) {
+  if (lane == 0) ((lds_u64 *)state)[i] += 1;
+}
+__device__ __forceinline__ OlapInfo ol_get(const lds_i32 *state, int32_t i) {
+  const lds_i32 *p = state + OVL_ST_OL + OVL_OL_INTS * i;
+  OlapInfo o;
+  o.s_lo = uni(p[0]); o.s_hi = uni(p[1]); o.t_lo = uni(p[2]); o.t_hi = uni(p[3]);
+  o.quality = uni(*(const lds_f64 *)(p + 4));
+  o.delta_ct = uni(p[6]);
+  o.slb = uni(p[7]); o.srb = uni(p[8]); o.tlb = uni(p[9]); o.trb = uni(p[10]);
+  o.min_diag = uni(p[11]); o.max_diag = uni(p[12]);
+  return o;
+}
+__device__ __forceinline__ void ol_put(lds_i32 *state, int32_t i, const OlapInfo &o,
+                                       uint32_t lane) {
+  lds_i32 *p = state + OVL_ST_OL + OVL_OL_INTS * i;
+  if (lane == 0) {
+    p[0] = o.s_lo; p[1] = o.s_hi; p[2] = o.t_lo; p[3] = o.t_hi;
+    *(lds_f64 *)(p + 4) = o.quality;
+    p[6] = o.delta_ct;
+    p[7] = o.slb; p[8] = o.srb; p[9] = o.tlb; p[10] = o.trb;
+    p[11] = o.min_diag; p[12] = o.max_diag;
+  }
+  lds_sync();
+}
+
 enum { K_NONE = 0, K_LEFT_BRANCH = 1, K_RIGHT_BRANCH = 2, K_DOVETAIL = 3 };
 
 struct ExtOut {
@@ -1117,13 +1179,14 @@ struct ExtOut {
 template <bool FAST, bool L16, int RJ, typename SS>
 __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS &S,
                                    int32_t S_Len, const SS &T, int32_t T_Len,
-                                   const WaveMem &WM, int32_t *stk, int32_t *RD,
-                                   int32_t *LD, uint32_t lane) {
+                                   const WaveMem &WM, int32_t *stk, int32_t *LD,
+                                   uint32_t lane) {
   // The match, the lengths and the row-loop results are wave-uniform: held in SGPRs they
   // survive the two row-loop calls without the per-lane spills a VGPR copy needs (141 -> 132
   // spill stores in the staged kernel; extension 217-218 -> 214-217 ms on 10k reads, r02v
-  // A/B, records identical).  SGPR copies of the pair's and unit's fields too (125 spill
-  // stores) measured the same, and were left out
+  // A/B, records identical).  Since round 7 the wave index, the pair's and unit's records and
+  // the strands are scalar from k_extend on (scratch loads / stores of the staged kernel's
+  // body 158 / 85 -> 27 / 17, profiles/r07a_isa.txt)
   Node M;
   M.Start = UNI(Mv.Start); M.Offset = UNI(Mv.Offset); M.Len = UNI(Mv.Len); M.Next = Mv.Next;
   S_Len = UNI(S_Len);
@@ -1138,7 +1201,8 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
   int32_t total = (M.Start < M.Offset ? M.Start : M.Offset) + M.Len +
                   (S_Right_Len < T_Right_Len ? S_Right_Len : T_Right_Len);
   int32_t error_limit = X.error_bound[total];
-  int32_t rd_len = 0, ld_len = 0;
+  int32_t rd_len = 0, ld_len = 0, rd_top = 0;
+  bool rd_neg = false, ld_neg = false;
   int32_t S_Hi, T_Hi, S_Lo, T_Lo;
 
   if (S_Right_Len == 0 || T_Right_Len == 0) {
@@ -1171,20 +1235,13 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
     rmte = po.mte;
     if (s_first) { S_Hi = po.a_len; T_Hi = po.t_len; }
     else         { T_Hi = po.a_len; S_Hi = po.t_len; }
-    // Set_Right_Delta: stack -> Right_Delta (forward.C:84-90)
+    // Set_Right_Delta (forward.C:84-90) is not a pass of its own: Right_Delta[i] is a function
+    // of two neighbouring stack entries, and its only reader is the merge into Left_Delta
+    // below, which reads the stack directly (the reverse call leaves the stack alone)
     if (po.nd >= 0) {
-      int32_t n = po.nd;
-      if (lane == 0) stk[n] = po.leftover + 1;     // "last + 1"
-      vm_sync();
-      n++;
-      for (int32_t i = lane; i < n - 1; i += 64) {
-        int32_t src = n - 1 - i;
-        int32_t a = stk[src], b = stk[src - 1];
-        int32_t v = (a < 0 ? -a : a) * ((b > 0) - (b < 0));
-        RD[i] = s_first ? -v : v;
-      }
-      vm_sync();
-      rd_len = n - 1;
+      rd_len = po.nd;
+      rd_top = po.leftover + 1;                    // the stack's last entry, "last + 1"
+      rd_neg = s_first;
     }
   }
   S_Hi += S_Right_Begin - 1;
@@ -1242,10 +1299,7 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
     }
     if (s_first) { S_Lo = a_end; T_Lo = t_end; }
     else         { T_Lo = a_end; S_Lo = t_end; }
-    if (!s_first && ld_len > 0) {
-      for (int32_t i = lane; i < ld_len; i += 64) LD[i] = -LD[i];
-      vm_sync();
-    }
+    ld_neg = !s_first;                             // applied with the merge below
   }
   S_Lo += S_Left_Begin + 1;
   T_Lo += T_Left_Begin + 1;
@@ -1253,14 +1307,22 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
   r.Errors = left_errors + right_errors;
   r.kind = (rmte == 0) ? ((lmte == 0) ? K_NONE : K_RIGHT_BRANCH)
                        : ((lmte == 0) ? K_LEFT_BRANCH : K_DOVETAIL);
-  if (lane == 0 && rd_len > 0) {
-    int32_t v;
-    if (RD[0] > 0) v = -(RD[0] + leftover + M.Len);
-    else           v = -(RD[0] - leftover - M.Len);
-    LD[ld_len] = v;
-  }
+  // Right_Delta[i] = +-|stack[n - i]| * sign(stack[n - 1 - i]) with n = rd_len and
+  // stack[n] = rd_top (forward.C:84-90, negated when S was the first string); merged behind
+  // the left deltas negated, the first one joined with the seed match (extend.C:213-224)
+  // (T was the reverse call's first string: its deltas change sign -- every lane rewrites
+  // the cells it reads, in the same pass)
+  if (ld_neg)
+    for (int32_t i = lane; i < ld_len; i += 64) LD[i] = -LD[i];
   if (rd_len > 0) {
-    for (int32_t i = 1 + lane; i < rd_len; i += 64) LD[ld_len + i] = -RD[i];
+    vm_sync();                                     // the forward traceback's stack stores
+    for (int32_t i = lane; i < rd_len; i += 64) {
+      const int32_t a = (i == 0) ? rd_top : stk[rd_len - i], b = stk[rd_len - 1 - i];
+      int32_t rd = (a < 0 ? -a : a) * ((b > 0) - (b < 0));
+      rd = rd_neg ? -rd : rd;
+      if (i == 0) rd = (rd > 0) ? rd + leftover + M.Len : rd - leftover - M.Len;
+      LD[ld_len + i] = -rd;
+    }
     ld_len += rd_len;
   }
   vm_sync();
@@ -1345,38 +1407,39 @@ __device__ Rec output_partial(uint32_t s_id, uint32_t t_id, int dir, const OlapI
 #define MIN_INTERSECTION 10
 #define SHIFT_SLACK 1
 
-// Add_Overlap (Process_String_Overlaps.C:222); wave-uniform
+// Add_Overlap (Process_String_Overlaps.C:222); wave-uniform, the overlaps in the wave's LDS
+// state block.
 // Returns the entry whose alignment was replaced by this one (new entry or better quality),
 // i.e. whose Left_Delta the reference memcpy()s, or -1.
 __device__ int32_t add_overlap(const ExtendArgs &X, int32_t s_lo, int32_t s_hi, int32_t t_lo,
-                               int32_t t_hi, double qual, int32_t delta_ct, OlapInfo *ol,
-                               int32_t &ct) {
+                               int32_t t_hi, double qual, int32_t delta_ct, lds_i32 *state,
+                               int32_t &ct, uint32_t lane) {
   if (!X.partial) {
     int32_t new_diag = t_lo - s_lo;
     for (int32_t i = 0; i < ct; i++) {
-      int32_t old_diag = ol[i].t_lo - ol[i].s_lo;
-      if ((new_diag > 0 && old_diag > 0 &&
-           ol[i].trb - new_diag - ol[i].slb >= MIN_INTERSECTION) ||
-          (new_diag <= 0 && old_diag <= 0 &&
-           ol[i].srb + new_diag - ol[i].tlb >= MIN_INTERSECTION)) {
-        if (new_diag < ol[i].min_diag) ol[i].min_diag = new_diag;
-        if (new_diag > ol[i].max_diag) ol[i].max_diag = new_diag;
-        if (s_lo < ol[i].slb) ol[i].slb = s_lo;
-        if (s_hi > ol[i].srb) ol[i].srb = s_hi;
-        if (t_lo < ol[i].tlb) ol[i].tlb = t_lo;
-        if (t_hi > ol[i].trb) ol[i].trb = t_hi;
-        if (qual < ol[i].quality) {
-          ol[i].s_lo = s_lo; ol[i].s_hi = s_hi; ol[i].t_lo = t_lo; ol[i].t_hi = t_hi;
-          ol[i].quality = qual;
-          ol[i].delta_ct = delta_ct;
-          return i;
+      OlapInfo o = ol_get(state, i);
+      int32_t old_diag = o.t_lo - o.s_lo;
+      if ((new_diag > 0 && old_diag > 0 && o.trb - new_diag - o.slb >= MIN_INTERSECTION) ||
+          (new_diag <= 0 && old_diag <= 0 && o.srb + new_diag - o.tlb >= MIN_INTERSECTION)) {
+        if (new_diag < o.min_diag) o.min_diag = new_diag;
+        if (new_diag > o.max_diag) o.max_diag = new_diag;
+        if (s_lo < o.slb) o.slb = s_lo;
+        if (s_hi > o.srb) o.srb = s_hi;
+        if (t_lo < o.tlb) o.tlb = t_lo;
+        if (t_hi > o.trb) o.trb = t_hi;
+        const bool better = qual < o.quality;
+        if (better) {
+          o.s_lo = s_lo; o.s_hi = s_hi; o.t_lo = t_lo; o.t_hi = t_hi;
+          o.quality = qual;
+          o.delta_ct = delta_ct;
         }
-        return -1;
+        ol_put(state, i, o, lane);
+        return better ? i : -1;
       }
     }
   }
   if (ct >= MAX_DISTINCT_OLAPS) return -1;
-  OlapInfo &o = ol[ct];
+  OlapInfo o;
   o.s_lo = o.slb = s_lo;
   o.s_hi = o.srb = s_hi;
   o.t_lo = o.tlb = t_lo;
@@ -1384,6 +1447,7 @@ __device__ int32_t add_overlap(const ExtendArgs &X, int32_t s_lo, int32_t s_hi, 
   o.quality = qual;
   o.delta_ct = delta_ct;
   o.min_diag = o.max_diag = t_lo - s_lo;
+  ol_put(state, ct, o, lane);
   ct++;
   return ct - 1;
 }
@@ -1512,12 +1576,12 @@ __device__ bool lies_on_alignment(int32_t start, int32_t offset, int32_t s_lo, i
 template <bool FAST, bool L16, bool ORD, int RJ, typename SS>
 __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &un,
                              const SS &S, const SS &T, const WaveMem &WM, int32_t *stk,
-                             int32_t *RD, int32_t *LD, unsigned long long *st, uint32_t lane,
-                             int32_t *ab) {
+                             int32_t *LD, uint32_t lane, int32_t *ab) {
   uint32_t S_ID = X.R.first_iid + un.r, T_ID = X.R.first_iid + P.tgt;
   int32_t S_Len = S.len, t_len = T.len;
   Node *nodes = X.pnodes + P.node_off;
   int32_t nn = (int32_t)P.node_cnt;
+  lds_i32 *state = WM.state;
   // the target's screened-end bits as its hash batch set them (PairRec bits 3 / 4): the
   // read flags themselves belong to whichever batch was built last
   const uint32_t trf = (P.flags >> 2) & 6u;
@@ -1532,7 +1596,7 @@ __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &
     if (!(ovl_len < (double)X.k))
       expct = (uint64_t)(int)floor(X.minkmer_exp * (ovl_len - X.k + 1));
     uint64_t mk = expct > X.filter_by_kmer_count ? expct : X.filter_by_kmer_count;
-    if (mk > (uint64_t)P.diag_ct) { st[2]++; return true; }
+    if (mk > (uint64_t)P.diag_ct) { st_inc(state, 2, lane); return true; }
   }
 
   // hopeless check (:433)
@@ -1552,12 +1616,11 @@ __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &
     } else {
       if (t_tail > 90 && !(trf & 4u)) hopeless = true;
     }
-    if (hopeless) { st[0]++; return true; }
+    if (hopeless) { st_inc(state, 0, lane); return true; }
   }
   if (X.dbg && lane == 0) atomicAdd(&X.dbg[8], 1ull);
 
-  OlapInfo ol[MAX_DISTINCT_OLAPS];
-  int32_t ct = 0;
+  int32_t ct = 0;                              // overlaps in the state block
   int32_t kind = K_NONE, S_Lo = 0, S_Hi = 0, T_Lo = 0, T_Hi = 0;
   int32_t remaining = nn;
   int32_t ld_len = 0;
@@ -1578,6 +1641,7 @@ __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &
       if (L > bv) { bv = L; bi = i; }
     }
     wave_argmax(bv, bi);
+    bi = uni(bi);
     Node M = nodes[bi];
     if (X.dbg && lane == 0) atomicAdd(&X.dbg[5], 1ull);
 #ifdef OVL_PROFILE
@@ -1593,7 +1657,7 @@ __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &
     }
     if (!hit_limit) {
       PROF_T(px0);
-      ExtOut eo = extend_alignment<FAST, L16, RJ>(X, M, S, S_Len, T, t_len, WM, stk, RD, LD, lane);
+      ExtOut eo = extend_alignment<FAST, L16, RJ>(X, M, S, S_Len, T, t_len, WM, stk, LD, lane);
 #ifdef OVL_PROFILE
       PROF_T(px1);
       if (X.dbg && lane == 0) atomicAdd(&X.dbg[15], px1 - px0);
@@ -1607,7 +1671,7 @@ __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &
           int32_t olap_len = 1 + ((S_Hi - S_Lo) < (T_Hi - T_Lo) ? (S_Hi - S_Lo) : (T_Hi - T_Lo));
           double quality = (double)eo.Errors / olap_len;
           if (eo.Errors <= X.error_bound[olap_len]) {
-            const int32_t slot = add_overlap(X, S_Lo, S_Hi, T_Lo, T_Hi, quality, ld_len, ol, ct);
+            const int32_t slot = add_overlap(X, S_Lo, S_Hi, T_Lo, T_Hi, quality, ld_len, state, ct, lane);
             if (X.window && slot >= 0) {               // memcpy(olap[i].delta, Left_Delta)
               int32_t *od = LD + (2 + slot) * (X.e_cap + 8);
               for (int32_t i = lane; i < ld_len; i += 64) od[i] = LD[i];
@@ -1701,78 +1765,84 @@ __device__ bool process_pair(const ExtendArgs &X, const PairRec &P, const Unit &
 
   int32_t outputs = 0;
   if (ct > 0) {
-    bool del[MAX_DISTINCT_OLAPS] = {false, false, false};
+    uint32_t del = 0;                        // bit i: overlap i is dropped
+    const uint32_t all = (1u << ct) - 1u;
     if (X.partial) {
       if (X.unique) {                       // Choose_Best_Partial (:336)
         int32_t best = 0;
-        double mb0 = (1.0 - ol[0].quality) *
-                     (2 + ol[0].s_hi - ol[0].s_lo + ol[0].t_hi - ol[0].t_lo);
+        const OlapInfo o0 = ol_get(state, 0);
+        double mb0 = (1.0 - o0.quality) * (2 + o0.s_hi - o0.s_lo + o0.t_hi - o0.t_lo);
+        double qbest = o0.quality;
         for (int32_t i = 1; i < ct; i++) {
-          double mb = (1.0 - ol[i].quality) *
-                      (2 + ol[i].s_hi - ol[i].s_lo + ol[i].t_hi - ol[i].t_lo);
-          if (mb0 < mb || (mb0 == mb && ol[i].quality < ol[best].quality)) best = i;
+          const OlapInfo o = ol_get(state, i);
+          double mb = (1.0 - o.quality) * (2 + o.s_hi - o.s_lo + o.t_hi - o.t_lo);
+          if (mb0 < mb || (mb0 == mb && o.quality < qbest)) { best = i; qbest = o.quality; }
         }
-        for (int32_t i = 0; i < ct; i++) del[i] = (i != best);
+        del = all & ~(1u << best);
       }
     } else if (X.unique) {                  // Combine_Into_One_Olap (:95)
       int32_t best = 0;
-      for (int32_t i = 1; i < ct; i++)
-        if (ol[i].quality < ol[best].quality) best = i;
-      for (int32_t i = 0; i < ct; i++) del[i] = (i != best);
+      double qbest = ol_get(state, 0).quality;
+      for (int32_t i = 1; i < ct; i++) {
+        const double q = ol_get(state, i).quality;
+        if (q < qbest) { best = i; qbest = q; }
+      }
+      del = all & ~(1u << best);
     } else {                                // Merge_Intersecting_Olaps (:153)
       for (int32_t i = 0; i < ct - 1; i++)
         for (int32_t j = i + 1; j < ct; j++) {
-          if (del[i] || del[j]) continue;
-          int32_t lo = ol[i].min_diag, hi = ol[i].max_diag;
-          if ((lo <= 0 && ol[j].min_diag > 0) || (lo > 0 && ol[j].min_diag <= 0)) continue;
-          if ((lo >= 0 && ol[j].trb - lo - ol[j].slb >= MIN_INTERSECTION) ||
-              (lo <= 0 && ol[j].srb + lo - ol[j].tlb >= MIN_INTERSECTION) ||
-              (hi >= 0 && ol[j].trb - hi - ol[j].slb >= MIN_INTERSECTION) ||
-              (hi <= 0 && ol[j].srb + hi - ol[j].tlb >= MIN_INTERSECTION)) {
-            int32_t keep, disc;
-            if (ol[i].quality < ol[j].quality) { keep = i; disc = j; del[j] = true; }
-            else                               { keep = j; disc = i; del[i] = true; }
-            if (ol[disc].min_diag < ol[keep].min_diag) ol[keep].min_diag = ol[disc].min_diag;
-            if (ol[disc].max_diag > ol[keep].max_diag) ol[keep].max_diag = ol[disc].max_diag;
-            if (ol[disc].slb < ol[keep].slb) ol[keep].slb = ol[disc].slb;
-            if (ol[disc].srb > ol[keep].srb) ol[keep].srb = ol[disc].srb;
-            if (ol[disc].tlb < ol[keep].tlb) ol[keep].tlb = ol[disc].tlb;
-            if (ol[disc].trb > ol[keep].trb) ol[keep].trb = ol[disc].trb;
+          if ((del >> i | del >> j) & 1u) continue;
+          const OlapInfo oi = ol_get(state, i), oj = ol_get(state, j);
+          int32_t lo = oi.min_diag, hi = oi.max_diag;
+          if ((lo <= 0 && oj.min_diag > 0) || (lo > 0 && oj.min_diag <= 0)) continue;
+          if ((lo >= 0 && oj.trb - lo - oj.slb >= MIN_INTERSECTION) ||
+              (lo <= 0 && oj.srb + lo - oj.tlb >= MIN_INTERSECTION) ||
+              (hi >= 0 && oj.trb - hi - oj.slb >= MIN_INTERSECTION) ||
+              (hi <= 0 && oj.srb + hi - oj.tlb >= MIN_INTERSECTION)) {
+            const bool keep_i = oi.quality < oj.quality;
+            OlapInfo keep = keep_i ? oi : oj;
+            const OlapInfo disc = keep_i ? oj : oi;
+            del |= 1u << (keep_i ? j : i);
+            if (disc.min_diag < keep.min_diag) keep.min_diag = disc.min_diag;
+            if (disc.max_diag > keep.max_diag) keep.max_diag = disc.max_diag;
+            if (disc.slb < keep.slb) keep.slb = disc.slb;
+            if (disc.srb > keep.srb) keep.srb = disc.srb;
+            if (disc.tlb < keep.tlb) keep.tlb = disc.tlb;
+            if (disc.trb > keep.trb) keep.trb = disc.trb;
+            ol_put(state, keep_i ? i : j, keep, lane);
           }
         }
     }
     for (int32_t i = 0; i < ct; i++) {
-      if (del[i]) continue;
+      if ((del >> i) & 1u) continue;
+      const OlapInfo o = ol_get(state, i);
       if (X.window) {
-        const int32_t rej = window_reject(X, un, P.tgt, ol[i], LD + (2 + i) * (X.e_cap + 8),
+        const int32_t rej = window_reject(X, un, P.tgt, o, LD + (2 + i) * (X.e_cap + 8),
                                           WM.rows, lane);
-        if (rej) { st[6 + rej]++; continue; }      // Bad_Short / Bad_Long_Window_Ct
+        if (rej) { st_inc(state, 6 + rej, lane); continue; }   // Bad_Short / Bad_Long_Window_Ct
       }
       Rec rec;
       int32_t bhg = 0;
-      if (X.partial) rec = output_partial(S_ID, T_ID, un.dir, ol[i], S_Len, t_len);
-      else           rec = output_overlap(S_ID, S_Len, un.dir, T_ID, t_len, ol[i], &bhg);
+      if (X.partial) rec = output_partial(S_ID, T_ID, un.dir, o, S_Len, t_len);
+      else           rec = output_overlap(S_ID, S_Len, un.dir, T_ID, t_len, o, &bhg);
       if (lane == 0) {
         uint32_t slot = atomicAdd(X.nout, 1u);
         if (slot < X.out_cap) X.out[slot] = rec;
         else atomicOr(X.overflow, 16u);
       }
       outputs++;
-      st[4]++;
+      st_inc(state, 4, lane);
       if constexpr (ORD) {                             // A / B_Olaps_For_Frag (:631-635)
-        if (ol[i].s_lo == 0) ab[0]++;
-        if (ol[i].s_hi >= S_Len - 1) ab[1]++;
+        if (o.s_lo == 0) ab[0]++;
+        if (o.s_hi >= S_Len - 1) ab[1]++;
       }
-      if (!X.partial) {
-        if (bhg <= 0) st[5]++;
-        else          st[6]++;
-      }
+      if (!X.partial) st_inc(state, bhg <= 0 ? 5 : 6, lane);
     }
   }
-  if (outputs == 0) st[0]++;
+  if (outputs == 0) st_inc(state, 0, lane);
   else {
-    st[1]++;
-    if (outputs > 1) st[3]++;
+    st_inc(state, 1, lane);
+    if (outputs > 1) st_inc(state, 3, lane);
   }
   return true;
 }
@@ -1814,7 +1884,8 @@ __device__ __forceinline__ int32_t wave_min_i32(int32_t v) {
 }
 
 #define OVL_SCR_STAGE 256        // the staged kernel's per-wave LDS scratch ints
-                                 // (Lies_On_Alignment thresholds, Left_Delta cache)
+                                 // (Lies_On_Alignment thresholds, Left_Delta cache); the
+                                 // wave's OVL_STATE_INTS follow them
 
 // STAGE = true: exception-free pairs, strands staged in LDS, rows in registers; pairs with
 // 'n' bases or a band wider than the register window are deferred to the generic kernel.
@@ -1836,7 +1907,11 @@ template <bool STAGE, bool L16, bool ORD = false, int RJ = OVL_RJ>
 __global__ void __launch_bounds__(512, RJ > OVL_RJ ? 3 : OVL_EXT_OCC)
 k_extend(ExtendArgs X) {
   extern __shared__ __attribute__((aligned(16))) int32_t s_ext0[];
-  uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // the wave index is wave-uniform but not provably so: as a scalar, everything computed
+  // from it (the wave's scratch and LDS pointers, its pair, the pair's records) stays in
+  // SGPRs across the row-loop calls instead of being spilled per lane
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wave = (uint32_t)uni((int32_t)(threadIdx.x >> 6));
   uint32_t gw = blockIdx.x * (blockDim.x >> 6) + wave;
   constexpr bool GR = !STAGE && L16;
   constexpr bool NOML = GR;                         // no LDS Edit_Match_Limit table
@@ -1856,7 +1931,7 @@ k_extend(ExtendArgs X) {
   lds_u64 *sw = nullptr, *tw = nullptr;
   if constexpr (STAGE) {
     // per wave: [S words | T words] (u64) then the scratch
-    uint32_t wave_ints = 4 * (uint32_t)X.sw_words + OVL_SCR_STAGE;
+    uint32_t wave_ints = 4 * (uint32_t)X.sw_words + OVL_SCR_STAGE + OVL_STATE_INTS;
     lds_i32 *wlds = s_ext + wave * wave_ints;
     sw = (lds_u64 *)wlds;
     tw = sw + X.sw_words;
@@ -1865,22 +1940,25 @@ k_extend(ExtendArgs X) {
     WM.tbw = wlds + 4 * X.sw_words;
     WM.ldc = WM.tbw;
     WM.ldcap = OVL_SCR_STAGE;
+    WM.state = WM.tbw + OVL_SCR_STAGE;
   } else {
     // per wave: row buffers (not with GR), traceback window, delta cache
     int32_t wcap = GR ? 0 : 2 * X.e_cap + 8;
-    uint32_t wave_ints = (2 * wcap + TB_ROWS * TB_W + OVL_LDCAP + 3) & ~3u;
+    uint32_t wave_ints = (2 * wcap + TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3u;
     lds_i32 *wlds = s_ext + wave * wave_ints;
     WM.lrow = wlds;
     WM.wcap = wcap;
     WM.tbw = WM.lrow + 2 * wcap;
     WM.ldc = WM.tbw + TB_ROWS * TB_W;
     WM.ldcap = OVL_LDCAP;
+    // 8-byte aligned for the 64-bit counters: wcap, OVL_LDCAP and TB_ROWS * TB_W are even
+    WM.state = WM.ldc + OVL_LDCAP;
   }
-  // per wave: stack | Right_Delta | Left_Delta | spare | the three olaps' delta copies (-w)
+  // per wave: stack | (unused) | Left_Delta | spare | the three olaps' delta copies (-w)
   int32_t *stk = X.deltas + (size_t)gw * 7 * (X.e_cap + 8);
-  int32_t *RD = stk + (X.e_cap + 8);
-  int32_t *LD = RD + (X.e_cap + 8);
-  unsigned long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t *LD = stk + 2 * (X.e_cap + 8);
+  if (lane < 9) ((lds_u64 *)WM.state)[lane] = 0;
+  lds_sync();
   const uint32_t npairs = X.npairs_dev ? __builtin_amdgcn_readfirstlane(*X.npairs_dev) : X.npairs;
 
   if constexpr (ORD) {
@@ -1897,7 +1975,7 @@ k_extend(ExtendArgs X) {
         Unit un = X.units[P.unit];
         Strand S = un.dir ? strand_rc(X.R, un.r) : strand_fwd(X.R, un.r);
         Strand T = strand_fwd(X.R, P.tgt);
-        process_pair<false, L16, true, OVL_RJ>(X, P, un, S, T, WM, stk, RD, LD, st, lane, ab);
+        process_pair<false, L16, true, OVL_RJ>(X, P, un, S, T, WM, stk, LD, lane, ab);
         lds_sync();
       };
       if ((uint64_t)(e - b) <= X.olim) {     // Process_String_Olaps.C:721
@@ -1913,13 +1991,13 @@ k_extend(ExtendArgs X) {
   for (;;) {
     uint32_t pi = 0;
     if (lane == 0) pi = atomicAdd(X.pair_next, 1u);
-    pi = __shfl(pi, 0);
+    pi = (uint32_t)uni((int32_t)pi);             // lane 0 is the first active lane
     if (pi >= npairs) break;
-    if (X.list) pi = X.list[pi];
-    PairRec P = X.pairs[pi];
-    Unit un = X.units[P.unit];
-    Strand S = un.dir ? strand_rc(X.R, un.r) : strand_fwd(X.R, un.r);
-    Strand T = strand_fwd(X.R, P.tgt);
+    if (X.list) pi = (uint32_t)uni((int32_t)X.list[pi]);
+    const PairRec P = uni_rec(X.pairs[pi]);
+    const Unit un = uni_rec(X.units[P.unit]);
+    const Strand S = uni_strand(un.dir ? strand_rc(X.R, un.r) : strand_fwd(X.R, un.r));
+    const Strand T = uni_strand(strand_fwd(X.R, P.tgt));
     if (X.restore) {
       // a pair deferred by an earlier launch may have had nodes removed (~Len) before it
       // stopped there
@@ -1961,7 +2039,7 @@ k_extend(ExtendArgs X) {
         StrandLP TL = stage_strand_span(T, tw, bw0, bw1, lane);
         lds_sync();
         PROF_T(pp0);
-        ok = process_pair<true, L16, false, RJ>(X, P, un, SL, TL, WM, stk, RD, LD, st, lane, nullptr);
+        ok = process_pair<true, L16, false, RJ>(X, P, un, SL, TL, WM, stk, LD, lane, nullptr);
 #ifdef OVL_PROFILE
         PROF_T(pp1);
         if (X.dbg && lane == 0) atomicAdd(&X.dbg[13], pp1 - pp0);
@@ -1969,13 +2047,15 @@ k_extend(ExtendArgs X) {
       }
       if (!ok && lane == 0) X.defer[atomicAdd(X.ndefer, 1u)] = pi;
     } else {
-      process_pair<false, L16, false, OVL_RJ>(X, P, un, S, T, WM, stk, RD, LD, st, lane, nullptr);
+      process_pair<false, L16, false, OVL_RJ>(X, P, un, S, T, WM, stk, LD, lane, nullptr);
     }
     lds_sync();
   }
   if (lane == 0)
-    for (int i = 0; i < 9; i++)
-      if (st[i]) atomicAdd(&X.stats[i < 7 ? i : i + 1], st[i]);
+    for (int i = 0; i < 9; i++) {
+      const unsigned long long v = ((lds_u64 *)WM.state)[i];
+      if (v) atomicAdd(&X.stats[i < 7 ? i : i + 1], v);
+    }
 }
 
 }  // namespace ovl
