@@ -96,6 +96,67 @@ def build_mhap_cli(force: bool = False, verbose: bool = True) -> str:
     return MHAP_CLI_OUT
 
 
+MERYL_OUT = os.path.join(OUT_DIR, "libcanu_meryl.so")
+MERYL_DEPS = [os.path.join(CSRC, "meryl.hip"), os.path.join(CSRC, "meryl_host.h"),
+              os.path.join(HERE, "..", "include", "canu_meryl.h")]
+MERYL_CLI_OUT = os.path.join(BIN_DIR, "meryl")
+EMT_CLI_OUT = os.path.join(BIN_DIR, "estimate-mer-threshold")
+
+
+def _stale(out: str, deps: list) -> bool:
+    return not os.path.exists(out) or \
+        any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps)
+
+
+def build_meryl(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_meryl.so: the k-mer count (meryl's frequent-mer step)."""
+    if not force and not _stale(MERYL_OUT, MERYL_DEPS):
+        return MERYL_OUT
+    os.makedirs(OUT_DIR, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, *HIPCC_FLAGS, "-o", MERYL_OUT + ".tmp", os.path.join(CSRC, "meryl.hip")]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(MERYL_OUT + ".tmp", MERYL_OUT)
+    return MERYL_OUT
+
+
+def build_meryl_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/meryl: the three meryl command lines canu's 0-mercounts stage runs (host
+    C++ over libcanu_meryl.so, found next to it through the rpath)."""
+    lib = build_meryl(verbose=verbose)
+    src = os.path.join(CSRC, "meryl_main.cpp")
+    deps = [src, lib, os.path.join(CSRC, "gkp_store.h"), *MERYL_DEPS[1:]]
+    if not force and not _stale(MERYL_CLI_OUT, deps):
+        return MERYL_CLI_OUT
+    os.makedirs(BIN_DIR, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
+           "-o", MERYL_CLI_OUT + ".tmp", src, "-L" + OUT_DIR, "-lcanu_meryl",
+           "-Wl,-rpath,$ORIGIN/../lib", "-Wl,--allow-shlib-undefined"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(MERYL_CLI_OUT + ".tmp", MERYL_CLI_OUT)
+    return MERYL_CLI_OUT
+
+
+def build_emt_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/estimate-mer-threshold: host only, no library."""
+    src = os.path.join(CSRC, "emt_main.cpp")
+    if not force and not _stale(EMT_CLI_OUT, [src]):
+        return EMT_CLI_OUT
+    os.makedirs(BIN_DIR, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-o", EMT_CLI_OUT + ".tmp", src]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(EMT_CLI_OUT + ".tmp", EMT_CLI_OUT)
+    return EMT_CLI_OUT
+
+
 def build(force: bool = False, verbose: bool = True, profile: bool = False) -> str:
     """profile=True builds the instrumented variant (in-kernel cycle stamps, OVL_DEBUG=1
     prints them) as libcanu_ovl_prof.so; load it with CANU_OVL_LIB."""
@@ -118,3 +179,6 @@ if __name__ == "__main__":
     if "--profile" not in sys.argv:
         build_mhap(force="--force" in sys.argv)
         build_cli(force="--force" in sys.argv)
+        build_meryl(force="--force" in sys.argv)
+        build_meryl_cli(force="--force" in sys.argv)
+        build_emt_cli(force="--force" in sys.argv)
