@@ -26,6 +26,7 @@
 #include "ovl_seed.hip"
 #include "ovl_extend.hip"
 #include "ovl_ovb.h"
+#include "ovl_plan.h"
 
 using namespace ovl;
 
@@ -158,10 +159,10 @@ struct ovl_ctx {
   int n_cu = 256;
   hipStream_t stream = nullptr;
   hipEvent_t ev[8];
-  // find_overlaps runs the extension of hash-batch chunk i on xstream while the probe and
-  // chain of chunk i+1 run on stream; xev[slot] / xev[2 + slot] bracket chunk i's extension
-  hipStream_t xstream = nullptr;
-  hipEvent_t xev[4];
+  // xev[0] / xev[1] bracket an extension launch (find_impl), which runs on `stream` like the
+  // probe and the chain: extending chunk i on a second stream beside chunk i+1's probe and
+  // chain was tried, measured 4-7 % slower, and removed
+  hipEvent_t xev[2];
 
   // tables
   int32_t max_errors = 0;
@@ -202,23 +203,21 @@ struct ovl_ctx {
 
   // find_overlaps working buffers: kept across calls (grow-only), hipMalloc of tens of
   // GB per call would cost seconds
-  // [2]: one per pipeline slot (chunk i's extension reads slot i & 1 while the chain of
-  // chunk i + 1 writes the other)
   struct {
-    DBuf<Unit> units[2];
+    DBuf<Unit> units;
     DBuf<uint64_t> rbase;
     DBuf<Probe> probe;
     DBuf<uint32_t> uhits, uflags, ctr, done, dset, big, defer, defer2, okey, oidx, okey2, oidx2;
     DBuf<uint32_t> live;          // the chain's units with at least one hit
-    DBuf<uint32_t> xctr[2], xnout;
+    DBuf<uint32_t> xctr, xnout;
     DBuf<unsigned long long> chits;
     DBuf<uint8_t> otmp;
     DBuf<uint64_t> ok64a, ok64b, dkey;       // -l orders
     DBuf<uint64_t> hcnt, hbase;              // ovl_seed_hits: per-unit hit counts / bases
     DBuf<uint4> hbuf;                        // ovl_seed_hits: one piece of the hit list
     DBuf<uint32_t> oa, ob, ucnt, useg;
-    DBuf<Node> pool, pnodes[2];
-    DBuf<PairRec> pairs[2];
+    DBuf<Node> pool, pnodes;
+    DBuf<PairRec> pairs;
     DBuf<unsigned long long> stats;
     DBuf<int32_t> rows, rowdir, deltas;
   } fb;
@@ -227,8 +226,6 @@ struct ovl_ctx {
   std::vector<uint32_t> h_lib;
   bool nohash_set = false;       // some read carries OVL_RFLAG_NOHASH
   uint32_t stats_hash_lib_lo = 0, stats_hash_lib_hi = UINT32_MAX;   // -H of the index
-  std::vector<uint32_t> ext_classes;       // read-length cap of each staged launch
-  uint32_t stats_ext_waves = 0, stats_gen_waves = 0;
   uint64_t index_records = 0;    // records of the current index (windows + skip markers)
   // an OverlapDriver job's phase 3 (ovl_overlap_driver): the index buffers are allocated for
   // the largest super-batch at once, and the search buffers keep the size the first search
@@ -301,6 +298,19 @@ struct ovl_ctx {
     return R;
   }
 };
+
+// the query reads of the loaded reads' libraries [lib_lo, lib_hi] (every library by default)
+static QueryRule query_rule(const ovl_ctx *c, uint32_t lib_lo = 0, uint32_t lib_hi = UINT32_MAX) {
+  QueryRule Q;
+  Q.len = c->h_len.data();
+  Q.lib = c->h_lib.empty() ? nullptr : c->h_lib.data();
+  Q.first_iid = c->first_iid;
+  Q.min_olap_len = c->P.min_olap_len;
+  Q.k = c->P.kmer_len;
+  Q.lib_lo = lib_lo;
+  Q.lib_hi = lib_hi;
+  return Q;
+}
 
 // ovl_probe_ceiling: Q independent random 16-B loads in flight per lane over the table's
 // 2^tab_bits slots (masked index, an LCG per lane: nothing in the loop but the loads)
@@ -436,20 +446,18 @@ int ovl_probe_replay(ovl_ctx *c, uint32_t bgn, uint32_t end, double *gloads_per_
   if (bgn < c->first_iid) bgn = c->first_iid;
   const uint32_t last = c->first_iid + c->nreads - 1;
   if (end > last) end = last;
-  // the query units of find_impl's rule (both orientations, --minlength, k), up to 2^28
+  // the query units (both orientations, --minlength, k) up to the read that passes 2^28
   // windows: a sample of the same lookup stream k_probe runs over these reads
   std::vector<Unit> units;
   std::vector<uint64_t> wb(1, 0);
   const uint32_t k = c->P.kmer_len;
-  for (uint32_t a = bgn; a <= end && a >= bgn && wb.back() < (1ull << 28); a++) {
-    const uint32_t r = a - c->first_iid;
-    const int32_t L = (int32_t)c->h_len[r];
-    if (L < c->P.min_olap_len || L < (int32_t)k) continue;
+  query_rule(c).each(bgn, end, [&](uint32_t a, bool, uint64_t w) {
+    if (!w || wb.back() >= (1ull << 28)) return;
     for (uint32_t dir = 0; dir < 2; dir++) {
-      units.push_back(Unit{r, dir});
-      wb.push_back(wb.back() + (uint64_t)(L - (int32_t)k + 1));
+      units.push_back(Unit{a - c->first_iid, dir});
+      wb.push_back(wb.back() + w);
     }
-  }
+  });
   const uint64_t n = wb.back();
   *n_windows = n;
   *gloads_per_s = 0.0;
@@ -593,14 +601,12 @@ int ovl_ctx_create(const ovl_params *p, int device, ovl_ctx **out) {
   c->device = device;
   c->n_cu = prop.multiProcessorCount;
   memset(&c->stats, 0, sizeof(c->stats));
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking) != hipSuccess) {
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
     delete c;
     return fail(OVL_ERR_HIP, "stream create failed");
   }
   for (int i = 0; i < 8; i++) (void)hipEventCreate(&c->ev[i]);
-  for (int i = 0; i < 4; i++) (void)hipEventCreate(&c->xev[i]);
+  for (int i = 0; i < 2; i++) (void)hipEventCreate(&c->xev[i]);
 
   double er = c->P.max_erate;
   c->max_errors = 1 + (int32_t)ceil(er * AS_MAX_READLEN);
@@ -630,13 +636,11 @@ void ovl_ctx_destroy(ovl_ctx *c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->xstream) (void)hipStreamSynchronize(c->xstream);
   for (int i = 0; i < 8; i++)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  for (int i = 0; i < 4; i++)
+  for (int i = 0; i < 2; i++)
     if (c->xev[i]) (void)hipEventDestroy(c->xev[i]);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->xstream) (void)hipStreamDestroy(c->xstream);
   delete c;
 }
 
@@ -1247,9 +1251,7 @@ static bool sq_bloom() {
 static size_t sq_held_bytes(const ovl_ctx *c);
 static void release_find_buffers(ovl_ctx *c) {
   auto &f = c->fb;
-  for (int i = 0; i < 2; i++) {
-    f.units[i].release(); f.pnodes[i].release(); f.pairs[i].release();
-  }
+  f.units.release(); f.pnodes.release(); f.pairs.release();
   f.rbase.release(); f.probe.release(); f.uhits.release();
   f.uflags.release(); f.done.release(); f.dset.release(); f.big.release(); f.live.release();
   f.defer.release(); f.defer2.release(); f.okey.release(); f.oidx.release();
@@ -1276,8 +1278,7 @@ static uint64_t index_window_cap(ovl_ctx *c) {
     const auto &f = c->fb;
     const uint64_t held = 2ull * c->d_tmpR.n * sizeof(Rec2) + 2ull * c->d_occ.n * 8 +
                           (uint64_t)c->d_tab.n * sizeof(TabEntry) + f.probe.n * sizeof(Probe) +
-                          (f.pool.n + f.pnodes[0].n + f.pnodes[1].n) * sizeof(Node) +
-                          (f.pairs[0].n + f.pairs[1].n) * sizeof(PairRec) +
+                          (f.pool.n + f.pnodes.n) * sizeof(Node) + f.pairs.n * sizeof(PairRec) +
                           4ull * (f.rows.n + f.rowdir.n + f.deltas.n) +
                           c->acc.units.n * sizeof(Unit) + c->acc.pnodes.n * sizeof(Node) +
                           c->acc.pairs.n * sizeof(PairRec) +
@@ -1544,17 +1545,13 @@ static int sq_prepare(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, u
     return OVL_OK;
   sq_release(c, false);
   const uint32_t k = c->P.kmer_len;
-  for (uint32_t a = bgn; a <= end && a >= bgn; a++) {         // find_impl's unit rule
-    const uint32_t r = a - c->first_iid;
-    const int32_t L = (int32_t)c->h_len[r];
-    const uint32_t lib = read_lib(c, r);
-    if (lib < lib_lo || lib > lib_hi || L < c->P.min_olap_len || L < (int32_t)k) continue;
-    for (uint32_t dir = 0; dir < 2; dir++) {
-      Q.units.push_back(Unit{r, dir});
+  query_rule(c, lib_lo, lib_hi).each(bgn, end, [&](uint32_t a, bool, uint64_t w) {
+    for (uint32_t dir = 0; w && dir < 2; dir++) {
+      Q.units.push_back(Unit{a - c->first_iid, dir});
       Q.ureadiid.push_back(a);
-      Q.uwin.push_back((uint64_t)(L - (int32_t)k + 1));
+      Q.uwin.push_back(w);
     }
-  }
+  });
   const uint32_t nu = (uint32_t)Q.units.size();
   if (nu == 0) return OVL_OK;
   // runs of <= RUN windows (hipcub sorts index with int)
@@ -1567,9 +1564,7 @@ static int sq_prepare(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, u
     ovl_ctx::SqRun R;
     R.u0 = u;
     R.e0 = total;
-    R.n = 0;
-    while (u < nu && (R.n + Q.uwin[u] <= RUN || u == R.u0)) R.n += Q.uwin[u++];
-    R.u1 = u;
+    R.u1 = u = take_within(Q.uwin, u, nu, RUN, &R.n);
     R.wb0 = Q.wb.size();
     uint64_t acc = 0;
     for (uint32_t x = R.u0; x < R.u1; x++) { Q.wb.push_back(acc); acc += Q.uwin[x]; }
@@ -1712,6 +1707,880 @@ static int sq_prepare(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, u
   return OVL_OK;
 }
 
+// ---- the extension's launch plan ---------------------------------------------------------
+// Pairs go through up to three launches: the staged kernel at full occupancy (8 waves per
+// <= 64 KB block) for pairs whose reads are both <= len1, the staged kernel with more LDS
+// per wave for reads <= len2, and the generic kernel for the rest (reads with an 'n',
+// bands wider than the register window, longer reads).  Each launch's scratch and LDS are
+// sized for its own length class, so one long read in a job does not shrink the others.
+struct ExtClass {
+  uint32_t len = 0, wpb = 1, waves = 0;
+  int32_t ecap = 0, sw = 0;
+  size_t lds = 0;
+  bool l16 = false;              // staged: 16-bit row log; generic: rows in global memory (GR)
+  uint64_t stride = 0;
+  bool wide = false;             // the 2 x OVL_RJ-chunk register window (wide bands)
+  uint64_t per_wave_bytes() const { return stride * 4 + 16ull * (ecap + 2) + 28ull * (ecap + 8); }
+};
+struct ExtPlan {
+  std::vector<ExtClass> stage;   // the staged launches in order; the wide class, if any, last
+  ExtClass gen;                  // the generic kernel: every read length
+  uint64_t rows_n = 0, rowdir_n = 0, deltas_n = 0;   // the scratch that fits every launch
+};
+
+// the k_extend instance of a launch: its address serves the attribute call, the occupancy
+// query and hipLaunchKernel
+static const void *extend_instance(bool staged, bool l16, bool ordered, bool wide) {
+#define OVL_KX(...) reinterpret_cast<const void *>(k_extend<__VA_ARGS__>)
+  if (staged && wide) return l16 ? OVL_KX(true, true, false, 2 * OVL_RJ) : OVL_KX(true, false, false, 2 * OVL_RJ);
+  if (staged) return l16 ? OVL_KX(true, true) : OVL_KX(true, false);
+  if (!ordered) return l16 ? OVL_KX(false, true) : OVL_KX(false, false);
+  return l16 ? OVL_KX(false, true, true) : OVL_KX(false, false, true);
+#undef OVL_KX
+}
+static int launch_extend(const ExtClass &g, bool staged, bool ordered, ExtendArgs &EA, hipStream_t s) {
+  void *args[] = {&EA};
+  HIPC(hipLaunchKernel(extend_instance(staged, g.l16, ordered, g.wide), dim3(g.waves / g.wpb),
+                       dim3(64 * g.wpb), args, g.lds, s));
+  return OVL_OK;
+}
+
+static int32_t ecap_of(const ovl_ctx *c, uint64_t L) {
+  return c->h_error_bound[std::min<uint64_t>(L, AS_MAX_READLEN)] + 2;
+}
+static int32_t sw_of(uint64_t L) { return (int32_t)(((L + 31) / 32 + 2) & ~1ull); }
+// per wave: the two strands' plane words, the scratch and the pair-state block
+static uint64_t stg_lds_of(uint64_t L) {
+  return 4ull * (4ull * (uint64_t)sw_of(L) + OVL_SCR_STAGE + OVL_STATE_INTS);
+}
+// a block's Edit_Match_Limit table
+static uint64_t ml_of(int32_t ec) { return 4ull * (((uint64_t)(ec + 2) + 3) & ~3ull); }
+// the longest read whose staged block of wpb waves fits cap bytes of LDS
+static uint32_t longest_fitting(const ovl_ctx *c, uint32_t wpb, size_t cap) {
+  auto fits = [&](uint64_t L) { return stg_lds_of(L) * wpb + ml_of(ecap_of(c, L)) <= cap; };
+  uint64_t lo = 0, hi = c->max_len;
+  if (fits(hi)) return (uint32_t)hi;
+  while (lo + 1 < hi) {
+    const uint64_t mid = (lo + hi) / 2;
+    if (fits(mid)) lo = mid; else hi = mid;
+  }
+  return (uint32_t)lo;
+}
+// the staged class of reads <= L within cap bytes of LDS per block
+static int make_stage(const ovl_ctx *c, bool window, uint32_t L, size_t cap, bool allow_knob,
+                      bool wide, ExtClass *out) {
+  ExtClass g;
+  g.len = L;
+  g.wide = wide;
+  g.ecap = ecap_of(c, L);
+  g.sw = sw_of(L);
+  g.l16 = L < 16384;
+  g.wpb = (uint32_t)std::min<uint64_t>(8, (cap - std::min<uint64_t>(cap, ml_of(g.ecap))) / stg_lds_of(L));
+  if (g.wpb < 1) return -1;
+  g.lds = stg_lds_of(L) * g.wpb + ml_of(g.ecap);
+  // experiment knob: OVL_EXT_BLOCKS_PER_CU pads the LDS so that at most that many blocks
+  // fit on a CU (occupancy studies); unset = natural occupancy
+  if (allow_knob)
+    if (const char *bp = getenv("OVL_EXT_BLOCKS_PER_CU")) {
+      int nb = atoi(bp);
+      if (nb > 0) g.lds = std::max<size_t>(g.lds, (160 * 1024) / nb - 256);
+    }
+  const uint64_t lw = wide ? std::max<uint64_t>(OVL_LOGW, 128 * OVL_RJ) : OVL_LOGW;
+  uint64_t st = (uint64_t)(g.ecap + 2) * lw / (g.l16 ? 2 : 1);   // the row log
+  if (window) st = std::max<uint64_t>(st, 3ull * (g.ecap + 9) + 2ull * L + 64);
+  g.stride = (st + 63) & ~63ull;
+  const void *kfn = extend_instance(true, g.l16, false, wide);
+  if (g.lds > 64 * 1024)
+    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds) != hipSuccess)
+      return -1;
+  // persistent grid: as many blocks as are resident at once (registers and LDS), so no
+  // block starts only after the work queue has drained; within the scratch budget
+  const uint64_t SCRATCH_BUDGET = 24ull << 30;
+  uint32_t waves = 4u * OVL_EXT_OCC * c->n_cu;
+  int bpc = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kfn, 64 * g.wpb, g.lds) == hipSuccess &&
+      bpc > 0)
+    waves = std::min<uint32_t>(waves, (uint32_t)bpc * g.wpb * c->n_cu);
+  while (waves > g.wpb && (uint64_t)waves * g.per_wave_bytes() > SCRATCH_BUDGET) waves /= 2;
+  g.waves = std::max<uint32_t>(g.wpb, (waves / g.wpb) * g.wpb);
+  *out = g;
+  return 0;
+}
+
+static int plan_extension(const ovl_ctx *c, bool window, bool ordered, ExtPlan *out) {
+  ExtPlan X;
+  // occupancy tiers of the staged kernel: 3 blocks of 8 waves per CU (the register limit),
+  // 3 blocks of 6, then blocks of up to 8 waves within 160 KB (as many as fit a CU).  A
+  // class's length is the span it stages (k_extend stages a pair's overlap span, not its
+  // whole reads): the tier's limit, or the longest loaded read when that is shorter, so a
+  // short-read job's launch is exactly what it was and a long-read job's pairs with shorter
+  // spans run at the higher occupancy.
+  uint32_t prev = 0;
+  const size_t tier_cap[3] = {52 * 1024, 52 * 1024, 160 * 1024};
+  const uint32_t tier_wpb[3] = {8, 6, 1};
+  ExtClass g;
+  for (int t = 0; t < 3; t++) {
+    const uint32_t T = longest_fitting(c, tier_wpb[t], tier_cap[t]);
+    const uint32_t L = std::min<uint32_t>(T, c->max_len);
+    if (L < 64 || L <= prev) continue;
+    if (make_stage(c, window, L, tier_cap[t], t == 0, false, &g))
+      return fail(OVL_ERR_HIP, "staged kernel setup");
+    X.stage.push_back(g);
+    prev = L;
+  }
+  // the wide class: the pairs of every staged class whose band outgrew the register window
+  // (the rest of their deferrals -- 'n' bases -- pass on to the generic kernel)
+  if (!X.stage.empty() && !getenv("OVL_NO_WIDE")) {
+    if (make_stage(c, window, X.stage.back().len, 160 * 1024, false, true, &g))
+      return fail(OVL_ERR_HIP, "wide staged kernel setup");
+    X.stage.push_back(g);
+  }
+  // the generic kernel: every read length; rows in LDS while two row buffers and the
+  // Edit_Match_Limit table fit a CU, else in global memory (GR)
+  ExtClass &gen = X.gen;
+  gen.len = c->max_len;
+  gen.ecap = ecap_of(c, c->max_len);
+  const size_t ml = ml_of(gen.ecap);
+  size_t w = 4ull * ((2ull * (2 * gen.ecap + 8) + TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3ull);
+  gen.l16 = w + ml > 160 * 1024;                       // GR
+  if (gen.l16) w = 4ull * ((TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3ull);
+  gen.wpb = (4 * w <= 80 * 1024) ? 4 : (2 * w <= 80 * 1024) ? 2 : 1;
+  gen.lds = w * gen.wpb + (gen.l16 ? 0 : ml);
+  uint64_t st = (uint64_t)(gen.ecap + 2) * (gen.ecap + 2) + 4ull * (gen.ecap + 2) + 64;
+  if (window) st = std::max<uint64_t>(st, 3ull * (gen.ecap + 9) + 2ull * c->max_len + 64);
+  // a wave's band-compact row log holds every row of one extension (quadratic in the
+  // error limit); past 2^28 ints the GR kernel checks its cursor and fails loudly
+  if (gen.l16) st = std::min<uint64_t>(st, 1ull << 28);
+  gen.stride = (st + 63) & ~63ull;
+  uint32_t waves = 24u * c->n_cu;
+  while (waves > gen.wpb && (uint64_t)waves * gen.per_wave_bytes() > (16ull << 30)) waves /= 2;
+  gen.waves = std::max<uint32_t>(gen.wpb, (waves / gen.wpb) * gen.wpb);
+  if (gen.lds > 64 * 1024)
+    HIPC(hipFuncSetAttribute(extend_instance(false, gen.l16, ordered, false),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen.lds));
+  X.rows_n = gen.stride * gen.waves;
+  X.rowdir_n = 4ull * (gen.ecap + 2) * gen.waves;
+  X.deltas_n = 7ull * (gen.ecap + 8) * gen.waves;
+  for (const ExtClass &s : X.stage) {
+    X.rows_n = std::max<uint64_t>(X.rows_n, s.stride * s.waves);
+    X.rowdir_n = std::max<uint64_t>(X.rowdir_n, 4ull * (s.ecap + 2) * s.waves);
+    X.deltas_n = std::max<uint64_t>(X.deltas_n, 7ull * (s.ecap + 8) * s.waves);
+  }
+  *out = X;
+  return OVL_OK;
+}
+
+// One random-lookup probe batch: nb units and their window bases (windows uwin[0..nb)) uploaded
+// to fb.units / fb.rbase, k_probe launched on the context's stream after event ev[2] -- not
+// waited for.  OVL_ERR_OOM, nothing launched: the buffers do not fit.
+static int probe_batch(ovl_ctx *c, const Unit *units, const uint64_t *uwin, uint32_t nb,
+                       bool bloom, std::vector<uint64_t> *rbase) {
+  auto &fb = c->fb;
+  hipStream_t s = c->stream;
+  rbase->resize(nb + 1);
+  uint64_t acc = 0;
+  for (uint32_t i = 0; i < nb; i++) { (*rbase)[i] = acc; acc += uwin[i]; }
+  (*rbase)[nb] = acc;
+  if (fb.units.grow(nb) || fb.rbase.grow(nb + 1) || fb.probe.grow(acc) || fb.uhits.grow(nb) ||
+      fb.uflags.grow(nb))
+    return fail(OVL_ERR_OOM, "probe buffers");
+  HIPC(hipMemcpyAsync(fb.units.p, units, sizeof(Unit) * nb, hipMemcpyHostToDevice, s));
+  HIPC(hipMemcpyAsync(fb.rbase.p, rbase->data(), 8ull * (nb + 1), hipMemcpyHostToDevice, s));
+  ProbeArgs PA;
+  PA.R = c->reads();
+  PA.X = index_dev(c);
+  if (bloom) {
+    PA.X.bloom = c->d_bloom.p;
+    PA.X.bloom_w = c->bloom_w;
+  }
+  PA.units = fb.units.p;
+  PA.rbase = fb.rbase.p;
+  PA.nunits = nb;
+  PA.out = fb.probe.p;
+  PA.unit_hits = fb.uhits.p;
+  PA.unit_flags = fb.uflags.p;
+  PA.k = c->P.kmer_len;
+  HIPC(hipEventRecord(c->ev[2], s));
+  if (bloom) hipLaunchKernelGGL(k_probe<true>, dim3((nb + 3) / 4), dim3(256), 0, s, PA);
+  else       hipLaunchKernelGGL(k_probe<false>, dim3((nb + 3) / 4), dim3(256), 0, s, PA);
+  HIPC(hipGetLastError());
+  return OVL_OK;
+}
+
+// ---- one search (find_impl) and its steps ------------------------------------------------
+// One probed batch of query units: what the chain needs of it.
+struct ProbedBatch {
+  uint32_t nb = 0;                 // units, uploaded to fb.units
+  std::vector<uint64_t> rbase;     // nb + 1 window bases within fb.probe, uploaded to fb.rbase
+  std::vector<uint32_t> uh;        // the units' seed hits
+  uint32_t *uflags = nullptr;      // device: the units' flags
+};
+
+// the accumulator's flush thresholds (see FindRun::acc_append)
+static const uint64_t ACC_PAIRS = 4ull << 20, ACC_NODES = 1ull << 30;
+// per staged class: its work-queue cursor and its defer count in the extension's counters
+static const uint32_t ctr_next[4] = {5, 11, 13, 15}, ctr_defer[4] = {8, 12, 14, 10};
+
+struct FindRun {
+  ovl_ctx *c;
+  hipStream_t s;
+  uint32_t k;
+  bool ordered;                    // -l: every pair through the ordered generic kernel
+  bool window;                     // -w
+  // A batch is sized by seed hits (node pool + list-ordered copy: 32 B per hit); the probe
+  // window budget adapts to the hits-per-window ratio seen so far (plan_chain)
+  uint64_t hit_budget = 0, win_budget = 512ull << 20, win_cap = 1536ull << 20;
+  uint64_t per_unit = 256;         // pairs per unit the chain first allows
+  uint32_t chain_waves = 0;
+  ExtPlan ext;
+  uint64_t nout_ub = 0;            // records: an upper bound (<= 3 per pair) of the device counter
+  bool pending = false;            // an extension launched and not yet collected
+  uint32_t pending_pairs = 0;
+
+  // The hit budget, the counters, the extension plan and its scratch, the output buffer.
+  int begin(size_t nunits) {
+    auto &fb = c->fb;
+    // seed hits per batch; halved while the chain buffers do not fit the HBM the index
+    // leaves, as the probe-slot cap is for the probe records
+    // 3.5 G: the 50k x 10 kb job in 2 chunks (1.27 s per step) rather than 4 (1.29 s) or 8
+    // (1.34 s) -- fewer re-probed windows and extension tails; node indices stay < 2^32
+    hit_budget = 3584ull << 20;
+    // within the HBM left beside the index: the node pool and its list-ordered copy take
+    // ~33 B per hit; keep them under 60 % of what is free now plus what they already hold
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
+      const uint64_t held = (fb.pool.n + fb.pnodes.n) * sizeof(Node);
+      hit_budget = std::min<uint64_t>(hit_budget, (uint64_t)((fr + held) * 0.6) / 33);
+    }
+    // a driver job's later searches chain within the buffers its first one sized (more hit
+    // chunks per run instead of a regrow of the pool and its copy)
+    if (c->sticky_budgets && fb.pnodes.n > (16ull << 20))
+      hit_budget = std::min<uint64_t>(hit_budget, fb.pnodes.n - 1);
+    if (const char *e = getenv("OVL_HIT_BUDGET_M"))             // experiments: millions of hits
+      hit_budget = std::max<uint64_t>(16, strtoull(e, nullptr, 10)) << 20;
+    hit_budget = std::max<uint64_t>(hit_budget, 16ull << 20);
+    if (const char *e = getenv("OVL_TEST_PAIRS_PER_UNIT"))      // test knob: force the regrow path
+      per_unit = std::max(1, atoi(e));
+    chain_waves = 4u * OVL_CHAIN_OCC * c->n_cu;   // OVL_CHAIN_OCC blocks of 4 waves per CU
+    if (fb.ctr.alloc(16) || fb.stats.alloc(16) || fb.xctr.alloc(16) || fb.xnout.alloc(1))
+      return fail(OVL_ERR_OOM, "counters");
+    HIPC(hipMemsetAsync(fb.stats.p, 0, 128, s));
+    if (int rc = plan_extension(c, window, ordered, &ext)) return rc;
+    if (fb.rows.alloc(ext.rows_n) || fb.rowdir.alloc(ext.rowdir_n) || fb.deltas.alloc(ext.deltas_n))
+      return fail(OVL_ERR_OOM, "extension scratch");
+    // records: the device counter xnout continues from the records already held (the
+    // driver's earlier hash batches)
+    uint32_t nout32 = (uint32_t)c->nout;
+    HIPC(hipMemcpyAsync(fb.xnout.p, &nout32, 4, hipMemcpyHostToDevice, s));
+    HIPC(hipStreamSynchronize(s));
+    nout_ub = c->nout;
+    return ensure_out(std::max<uint64_t>(c->nout + (1u << 20), c->nout + nunits * 8));
+  }
+
+  int ensure_out(uint64_t need) {
+    if (need <= c->d_out.n && c->d_out.p) return OVL_OK;
+    HIPC(hipStreamSynchronize(s));
+    uint32_t cur = 0;
+    HIPC(hipMemcpy(&cur, c->fb.xnout.p, 4, hipMemcpyDeviceToHost));
+    DBuf<Rec> bigger;
+    if (bigger.alloc(need + (need >> 2))) return fail(OVL_ERR_OOM, "output grow");
+    if (cur)
+      HIPC(hipMemcpyAsync(bigger.p, c->d_out.p, sizeof(Rec) * cur, hipMemcpyDeviceToDevice, s));
+    HIPC(hipStreamSynchronize(s));
+    std::swap(bigger.p, c->d_out.p);
+    std::swap(bigger.n, c->d_out.n);
+    return OVL_OK;
+  }
+
+  // The launched extension has finished: its counters, class split and time.
+  int collect_extension() {
+    if (!pending) return OVL_OK;
+    pending = false;
+    HIPC(hipEventSynchronize(c->xev[1]));
+    uint32_t hx[16];
+    HIPC(hipMemcpy(hx, c->fb.xctr.p, 64, hipMemcpyDeviceToHost));
+    float t = 0;
+    (void)hipEventElapsedTime(&t, c->xev[0], c->xev[1]);
+    c->stats.ms_extend += t;
+    if (hx[7] & 32u)
+      return fail(OVL_ERR_UNSUPPORTED, "an extension needs more than 2^28 row cells (error limit "
+                  "%d of a %u-base read): past the generic kernel's per-wave row log",
+                  ecap_of(c, c->max_len), c->max_len);
+    if (hx[7]) return fail(OVL_ERR_HIP, "extension capacity exceeded (flags %u)", hx[7]);
+    uint32_t left = pending_pairs;
+    for (size_t ci = 0; ci < ext.stage.size() && !ordered; ci++) {
+      const uint32_t nd = hx[ctr_defer[ci]];
+      if (getenv("OVL_DEBUG"))
+        fprintf(stderr, "OVL_DEBUG class %zu (reads <= %u): deferred %u of %u pairs\n", ci,
+                ext.stage[ci].len, nd, left);
+      if (ci == 0) c->stats.staged_pairs += left - nd;
+      else c->stats.long_pairs += left - nd;
+      left = nd;
+    }
+    c->stats.generic_pairs += left;
+    return OVL_OK;
+  }
+
+  // -l: the reference's two pair orders per unit (see k_olim_keys), String_Olap_Space order and
+  // By_Diag_Sum order, by stable radix sorts
+  int order_pairs_olim(const PairRec *pairs, const Node *pnodes, uint32_t npairs,
+                                uint32_t nc, ExtendArgs *EA) {
+    auto &fb = c->fb;
+    const int n = (int)npairs;
+    size_t t1 = 0, t2 = 0, t3 = 0;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, fb.okey.p, fb.okey2.p, fb.oa.p,
+                                            fb.ob.p, n, 0, 32, s));
+    HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, fb.ok64a.p, fb.ok64b.p, fb.oa.p,
+                                            fb.ob.p, n, 0, 64, s));
+    HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, fb.ucnt.p, fb.useg.p, (int)nc + 1, s));
+    const size_t tmp = std::max(std::max(t1, t2), t3);
+    HIPC(hipStreamSynchronize(s));
+    if (fb.okey.grow(npairs) || fb.okey2.grow(npairs) || fb.oa.grow(npairs) ||
+        fb.ob.grow(npairs) || fb.oidx.grow(npairs) || fb.oidx2.grow(npairs) ||
+        fb.ok64a.grow(npairs) || fb.ok64b.grow(npairs) || fb.dkey.grow(npairs) ||
+        fb.ucnt.grow((size_t)nc + 1) || fb.useg.grow((size_t)nc + 1) ||
+        fb.otmp.grow(std::max<size_t>(tmp, 1)))
+      return fail(OVL_ERR_OOM, "-l pair orders");
+    const dim3 grid(std::min<uint32_t>((npairs + 255) / 256, 4096)), blk(256);
+    HIPC(hipMemsetAsync(fb.ucnt.p, 0, 4ull * (nc + 1), s));
+    // first-hit order: by ~tgt, then (stably) by (unit, diag_bgn)
+    hipLaunchKernelGGL(k_olim_keys, grid, blk, 0, s, pairs, pnodes, npairs, (int32_t)k,
+                       fb.okey.p, fb.ok64a.p, fb.oa.p, fb.dkey.p, fb.ucnt.p);
+    HIPC(hipGetLastError());
+    HIPC(hipcub::DeviceScan::ExclusiveSum(fb.otmp.p, t3, fb.ucnt.p, fb.useg.p, (int)nc + 1, s));
+    size_t tt = t1;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.okey.p, fb.okey2.p, fb.oa.p,
+                                            fb.ob.p, n, 0, 32, s));
+    hipLaunchKernelGGL(k_gather_u64, grid, blk, 0, s, fb.ok64a.p, fb.ob.p, npairs, fb.ok64b.p);
+    tt = t2;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.ok64b.p, fb.ok64a.p, fb.ob.p,
+                                            fb.oa.p, n, 0, 64, s));
+    // String_Olap_Space indices, then the order by (unit, index)
+    hipLaunchKernelGGL(k_olim_slots, dim3(std::min<uint32_t>((nc + 3) / 4, 8192)), blk, 0, s,
+                       pairs, fb.oa.p, fb.useg.p, nc,
+                       c->first_iid - c->hash_bgn_iid, fb.ok64b.p, fb.ob.p);
+    HIPC(hipGetLastError());
+    tt = t2;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.ok64b.p, fb.ok64a.p, fb.ob.p,
+                                            fb.oidx.p, n, 0, 64, s));       // oidx: ord_slot
+    // By_Diag_Sum: stably by the diagonal key, then stably by unit
+    hipLaunchKernelGGL(k_gather_u64, grid, blk, 0, s, fb.dkey.p, fb.oidx.p, npairs, fb.ok64a.p);
+    tt = t2;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.ok64a.p, fb.ok64b.p, fb.oidx.p,
+                                            fb.oa.p, n, 0, 64, s));
+    hipLaunchKernelGGL(k_gather_unit, grid, blk, 0, s, pairs, fb.oa.p, npairs, fb.okey.p);
+    tt = t1;
+    HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.okey.p, fb.okey2.p, fb.oa.p,
+                                            fb.oidx2.p, n, 0, 32, s));      // oidx2: ord_diag
+    HIPC(hipGetLastError());
+    EA->useg = fb.useg.p;
+    EA->ord_slot = fb.oidx.p;
+    EA->ord_diag = fb.oidx2.p;
+    EA->dkey = fb.dkey.p;
+    return OVL_OK;
+  }
+
+  // longest-first work order (node count descending; ties keep pair order), and the defer lists
+  int order_pairs_longest_first(const PairRec *pairs, uint32_t npairs, ExtendArgs *EA) {
+    auto &fb = c->fb;
+    size_t tmp = 0;
+    HIPC(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, fb.okey.p, fb.okey2.p,
+                                                      fb.oidx.p, fb.oidx2.p, (int)npairs, 0,
+                                                      32, s));
+    if (fb.okey.n < npairs || fb.oidx.n < npairs || fb.okey2.n < npairs || fb.oidx2.n < npairs ||
+        fb.defer.n < npairs || fb.defer2.n < npairs || fb.otmp.n < tmp || !fb.otmp.p) {
+      HIPC(hipStreamSynchronize(s));
+      if (fb.okey.grow(npairs) || fb.oidx.grow(npairs) || fb.okey2.grow(npairs) ||
+          fb.oidx2.grow(npairs) || fb.defer.grow(npairs) || fb.defer2.grow(npairs) ||
+          fb.otmp.grow(std::max<size_t>(tmp, 1)))
+        return fail(OVL_ERR_OOM, "work order");
+    }
+    if (npairs > 1) {
+      hipLaunchKernelGGL(k_pair_order_keys, dim3(std::min<uint32_t>((npairs + 255) / 256, 4096)),
+                         dim3(256), 0, s, pairs, npairs, fb.okey.p, fb.oidx.p);
+      HIPC(hipGetLastError());
+      HIPC(hipcub::DeviceRadixSort::SortPairsDescending(fb.otmp.p, tmp, fb.okey.p, fb.okey2.p,
+                                                        fb.oidx.p, fb.oidx2.p, (int)npairs, 0,
+                                                        32, s));
+      EA->list = fb.oidx2.p;
+    }
+    return OVL_OK;
+  }
+
+  // One chunk's (or the accumulator's) pairs through the extension kernels, the host not waiting
+  // for the last one: work order, the staged classes, the generic kernel; collect_extension()
+  // reads its counters back.
+  int launch_extension(const Unit *units, PairRec *pairs, Node *pnodes, uint32_t npairs,
+                                uint32_t nc) {
+    auto &fb = c->fb;
+    uint32_t *x_ctr = fb.xctr.p;
+    nout_ub += 3ull * npairs;
+    if (int rc = ensure_out(nout_ub)) return rc;
+    ExtendArgs EA = {};              // every field not set here is 0 / null
+    EA.R = c->reads();
+    EA.units = units;
+    EA.pairs = pairs;
+    EA.npairs = npairs;
+    EA.pnodes = pnodes;
+    EA.pair_next = x_ctr + 5;
+    EA.error_bound = c->d_error_bound.p;
+    EA.match_limit = c->d_match_limit.p;
+    EA.max_errors = c->max_errors;
+    EA.branch_match_value = c->branch_match_value;
+    EA.min_branch_tail_slope = c->min_branch_tail_slope;
+    EA.min_branch_end_dist = 20;
+    EA.partial = c->P.partial;
+    EA.unique = c->P.unique_olap_per_pair;
+    EA.min_olap_len = c->P.min_olap_len;
+    EA.use_hopeless = c->P.use_hopeless_check;
+    EA.k = (int32_t)k;
+    EA.filter_by_kmer_count = c->P.filter_by_kmer_count;
+    EA.minkmer_exp = exp(-1.0 * (double)k * c->P.max_erate);
+    EA.rows = fb.rows.p;
+    EA.rowdir = fb.rowdir.p;
+    EA.deltas = fb.deltas.p;
+    EA.out = c->d_out.p;
+    EA.nout = fb.xnout.p;
+    EA.out_cap = (uint32_t)std::min<uint64_t>(c->d_out.n, 0xFFFFFFF0ull);
+    EA.stats = fb.stats.p;
+    EA.window = window ? 1 : 0;
+    EA.overflow = x_ctr + 7;
+    if (getenv("OVL_DEBUG")) {
+      if (!c->dbg.p) {
+        HIPC(hipStreamSynchronize(s));
+        if (c->dbg.alloc(32)) return fail(OVL_ERR_OOM, "debug counters");
+        HIPC(hipMemsetAsync(c->dbg.p, 0, 256, s));
+      }
+      EA.dbg = c->dbg.p;
+    }
+    EA.olim = c->P.frag_olap_limit;
+    EA.nunits = nc;
+    pending_pairs = npairs;
+    HIPC(hipMemsetAsync(x_ctr, 0, 64, s));
+    if (npairs && ordered)
+      if (int rc = order_pairs_olim(pairs, pnodes, npairs, nc, &EA)) return rc;
+    if (npairs && !ordered)
+      if (int rc = order_pairs_longest_first(pairs, npairs, &EA)) return rc;
+    HIPC(hipEventRecord(c->xev[0], s));
+    // the generic kernel's arguments
+    auto generic_args = [](ExtendArgs &A, const ExtClass &gen, uint32_t *ctr) {
+      A.e_cap = gen.ecap;
+      A.rows_cap = gen.stride;
+      A.sw_words = 0;
+      A.pair_next = ctr + 9;
+      A.defer = nullptr;
+      A.ndefer = nullptr;
+    };
+    // the host reads a class's defer count before the next launch: a launch whose input list is
+    // empty is skipped (the bench job's one staged launch then is the extension's only launch)
+    auto deferred = [&](size_t ci, uint32_t *nd) -> int {
+      HIPC(hipMemcpyAsync(nd, x_ctr + ctr_defer[ci], 4, hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      return OVL_OK;
+    };
+    if (npairs && ordered) {
+      generic_args(EA, ext.gen, x_ctr);
+      c->stats.extend_launches++;
+      if (int rc = launch_extend(ext.gen, false, true, EA, s)) return rc;
+    } else if (npairs) {
+      // the staged classes in turn, each deferring what it cannot take to the next list
+      // (whose length the next launch reads from the device counter); the generic kernel
+      // takes the last list, or every pair when no class exists
+      uint32_t *defer_buf[2] = {fb.defer.p, fb.defer2.p};
+      uint32_t nd = 1;                   // pairs the previous class left
+      for (size_t ci = 0; ci < ext.stage.size(); ci++) {
+        const ExtClass &g = ext.stage[ci];
+        EA.e_cap = g.ecap;
+        EA.rows_cap = g.stride;
+        EA.sw_words = g.sw;
+        EA.pair_next = x_ctr + ctr_next[ci];
+        EA.defer = defer_buf[ci & 1];
+        EA.ndefer = x_ctr + ctr_defer[ci];
+        if (ci > 0)
+          if (int rc = deferred(ci - 1, &nd)) return rc;
+        if (nd) {                        // an empty class defers nothing: its counter stays 0
+          c->stats.extend_launches++;
+          if (int rc = launch_extend(g, true, false, EA, s)) return rc;
+        }
+        EA.list = defer_buf[ci & 1];
+        EA.npairs_dev = x_ctr + ctr_defer[ci];
+        EA.restore = 1;          // a deferred pair may have had nodes removed (~Len)
+      }
+      generic_args(EA, ext.gen, x_ctr);
+      if (!ext.stage.empty())
+        if (int rc = deferred(ext.stage.size() - 1, &nd)) return rc;
+      if (nd) {
+        c->stats.extend_launches++;
+        if (int rc = launch_extend(ext.gen, false, false, EA, s)) return rc;
+      }
+    }
+    HIPC(hipEventRecord(c->xev[1], s));
+    pending = true;
+    return OVL_OK;
+  }
+
+  // Extend everything the accumulator holds; it is empty again for the next chunk (the
+  // stream orders the next appends after this launch's reads).
+  int flush_acc() {
+    if (int rc = collect_extension()) return rc;
+    auto &A = c->acc;
+    int rc = launch_extension(A.units.p, A.pairs.p, A.pnodes.p, (uint32_t)A.np, (uint32_t)A.nu);
+    A.nu = A.nn = A.np = 0;
+    return rc;
+  }
+
+  // Append a chunk's units, list nodes and pairs to the accumulator (device copies on the
+  // stream the extension also runs on: nothing is overwritten early).
+  int acc_append(const Unit *u, uint32_t nu_c, const Node *nodes, uint64_t nn_c,
+                          const PairRec *pairs, uint32_t np_c) {
+    auto &A = c->acc;
+    if (A.nu + nu_c >= 0xFFFFFFF0ull || A.nn + nn_c >= 0xFFFFFFF0ull)
+      return fail(OVL_ERR_UNSUPPORTED, "extension accumulator past 2^32 entries");
+    auto acc_fits = [&]() {
+      return A.units.n >= A.nu + nu_c && A.pnodes.n >= A.nn + nn_c && A.pairs.n >= A.np + np_c;
+    };
+    // once it holds a launch's worth (a quarter of the flush thresholds), what the
+    // accumulator holds is extended rather than moved into bigger buffers: a regrow on a full
+    // device costs ~1 s (the full-size configs[4] job, r05e), while smaller launches lose to
+    // their tails (one launch per search: extension 8.4 -> 23 s, r05f)
+    if (!acc_fits() && (A.np >= ACC_PAIRS / 4 || A.nn >= ACC_NODES / 4))
+      if (int rc = flush_acc()) return rc;
+    if (!acc_fits()) {
+      // growing moves the buffers: the pending extension (which reads them) must be done,
+      // and what the accumulator holds is carried over
+      HIPC(hipStreamSynchronize(s));
+      // a buffer moved into one of at least `need` entries, its first `used` kept
+      auto regrow = [](auto &buf, uint64_t used, uint64_t need) -> int {
+        if (buf.n >= need && buf.p) return OVL_OK;
+        typename std::remove_reference<decltype(buf)>::type bigger;
+        if (bigger.alloc(std::max<uint64_t>(need, buf.n + buf.n / 2))) return -1;
+        if (used) HIPC(hipMemcpy(bigger.p, buf.p, used * sizeof(*buf.p), hipMemcpyDeviceToDevice));
+        std::swap(bigger.p, buf.p);
+        std::swap(bigger.n, buf.n);
+        return OVL_OK;
+      };
+      if (regrow(A.units, A.nu, A.nu + nu_c) || regrow(A.pnodes, A.nn, A.nn + nn_c) ||
+          regrow(A.pairs, A.np, A.np + np_c)) {
+        // no room for bigger buffers beside the ones being copied (a device nearly full of
+        // sorted windows, index and search buffers): what the accumulator holds is extended
+        // now, and the emptied buffers are freed before this chunk's own are allocated
+        if (A.nu || A.nn || A.np) {
+          if (int rc = flush_acc()) return rc;
+          HIPC(hipStreamSynchronize(s));
+        }
+        if ((A.units.n < nu_c && A.units.alloc(nu_c)) ||
+            (A.pnodes.n < nn_c && A.pnodes.alloc(nn_c)) || (A.pairs.n < np_c && A.pairs.alloc(np_c)))
+          return fail(OVL_ERR_OOM, "extension accumulator (%llu nodes)", (unsigned long long)nn_c);
+      }
+    }
+    if (nu_c)
+      HIPC(hipMemcpyAsync(A.units.p + A.nu, u, sizeof(Unit) * nu_c, hipMemcpyDeviceToDevice, s));
+    if (nn_c)
+      HIPC(hipMemcpyAsync(A.pnodes.p + A.nn, nodes, sizeof(Node) * nn_c, hipMemcpyDeviceToDevice, s));
+    if (np_c) {
+      hipLaunchKernelGGL(k_append_pairs, dim3(std::min<uint32_t>((np_c + 255) / 256, 4096)),
+                         dim3(256), 0, s, pairs, np_c, (uint32_t)A.nu, (uint32_t)A.nn,
+                         A.pairs.p + A.np);
+      HIPC(hipGetLastError());
+    }
+    A.nu += nu_c;
+    A.nn += nn_c;
+    A.np += np_c;
+    return OVL_OK;
+  }
+
+  // The units from u0 on that fit the window budget, probed by random lookups.
+  int probe_lookup(const std::vector<Unit> &units, const std::vector<uint64_t> &uwin,
+                            uint32_t u0, bool bloom, ProbedBatch *B) {
+    for (;;) {
+      B->nb = take_within(uwin, u0, (uint32_t)units.size(), win_budget) - u0;
+      const int rc = probe_batch(c, units.data() + u0, uwin.data() + u0, B->nb, bloom, &B->rbase);
+      if (rc == OVL_OK) break;
+      if (rc != OVL_ERR_OOM || B->nb == 1 || win_budget <= (16ull << 20)) return rc;
+      win_cap = win_budget = win_budget / 2;
+    }
+    const uint32_t nb = B->nb;
+    c->stats.probe_launches++;
+    HIPC(hipEventRecord(c->ev[3], s));
+    B->uh.resize(nb);
+    HIPC(hipMemcpyAsync(B->uh.data(), c->fb.uhits.p, 4ull * nb, hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    float t = 0;
+    (void)hipEventElapsedTime(&t, c->ev[2], c->ev[3]);
+    c->stats.ms_seed += t;
+    c->stats.ms_probe_kernel += t;
+    const uint64_t nwin = B->rbase[nb];
+    if (getenv("OVL_TIMING"))
+      fprintf(stderr, "OVL_TIMING probe launch: %u units, %llu windows, %.3f ms\n", nb,
+              (unsigned long long)nwin, t);
+    // algorithmic bytes: per window one 16-B table entry and one 8-B Probe record, plus the
+    // packed query (2 bits per base); see DESIGN.md
+    c->stats.probe_bytes += nwin * 24 + nwin / 4;
+    B->uflags = c->fb.uflags.p;
+    return OVL_OK;
+  }
+
+  // The run of sorted windows holding unit u0: probed once per batch (k_probe_sorted), its
+  // records then chained in hit-budget chunks.  *sq_run: the run; *run_uh: its units' hits.
+  int probe_sorted_run(const std::vector<Unit> &units, uint32_t u0, size_t *sq_run,
+                                std::vector<uint32_t> *run_uh, ProbedBatch *B) {
+    auto &fb = c->fb;
+    auto &Q = c->sq;
+    const uint32_t nu = (uint32_t)units.size();
+    while (Q.runs[*sq_run].u1 <= u0) (*sq_run)++;
+    const auto &R = Q.runs[*sq_run];
+    const uint32_t ue = std::min<uint32_t>(R.u1, nu);
+    if (Q.probed != (int)*sq_run) {
+      const uint64_t wlim = Q.wb[R.wb0 + (ue - R.u0)];
+      if (fb.probe.grow(R.n)) return fail(OVL_ERR_OOM, "probe records (%llu)", (unsigned long long)R.n);
+      HIPC(hipEventRecord(c->ev[4], s));           // the probe step: seed-phase time
+      HIPC(hipMemsetAsync(fb.probe.p, 0, 8ull * wlim, s));
+      HIPC(hipMemsetAsync(Q.uflags.p + R.u0, 0, 4ull * (ue - R.u0), s));
+      HIPC(hipMemsetAsync(Q.uhits.p + R.u0, 0, 4ull * (ue - R.u0), s));
+      SqProbeArgs SA;
+      SA.X = index_dev(c);
+      if (c->bloom_ok && sq_bloom()) {        // the filter in front of the table
+        SA.X.bloom = c->d_bloom.p;
+        SA.X.bloom_w = c->bloom_w;
+      }
+      SA.R = c->reads();
+      SA.key = Q.key.p + R.e0;
+      SA.wid = Q.wid.p + R.e0;
+      SA.n = R.n;
+      SA.wlim = (uint32_t)wlim;
+      SA.units = Q.dunits.p + R.u0;
+      SA.wbase = Q.dwbase.p + R.wb0;
+      SA.ublk = Q.ublk.p + R.ub0;
+      SA.k = k;
+      SA.out = fb.probe.p;
+      SA.unit_flags = Q.uflags.p + R.u0;
+      SA.unit_hits = Q.uhits.p + R.u0;
+      // the kernel alone is timed (the records' zeroing and the unit hit counts around it
+      // are not the probe's bytes)
+      HIPC(hipEventRecord(c->ev[2], s));
+      hipLaunchKernelGGL(k_probe_sorted, dim3(8 * c->n_cu), dim3(256), 0, s, SA);
+      HIPC(hipEventRecord(c->ev[3], s));
+      c->stats.probe_launches++;
+      c->stats.probe_sorted_launches++;
+      HIPC(hipGetLastError());
+      HIPC(hipEventRecord(c->ev[5], s));
+      run_uh->resize(ue - R.u0);
+      HIPC(hipMemcpyAsync(run_uh->data(), Q.uhits.p + R.u0, 4ull * (ue - R.u0),
+                          hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      float t = 0, tstep = 0;
+      (void)hipEventElapsedTime(&t, c->ev[2], c->ev[3]);
+      (void)hipEventElapsedTime(&tstep, c->ev[4], c->ev[5]);
+      c->stats.ms_probe_kernel += t;
+      c->stats.ms_seed += std::max(t, tstep);          // beside the kernel: the records' zeroing
+      // algorithmic bytes: the sorted windows (8-B key + 4-B id), and the table and its
+      // filter read once each -- or, when they are larger than the run (a full-size
+      // configs[4] super-batch's 68.7 GB table against a run of 2^29 windows), at most one
+      // entry and one filter word per window (the hits' 8-B records are not counted)
+      const uint64_t tab_b = 16ull << c->tab_bits;
+      const uint64_t flt_b = SA.X.bloom ? 8ull * ((1ull << (c->tab_bits - c->slice_bits)) << c->bloom_w) : 0ull;
+      c->stats.probe_bytes += 12ull * R.n + std::min<uint64_t>(tab_b, 16ull * R.n) +
+                              std::min<uint64_t>(flt_b, 8ull * R.n);
+      Q.probed = (int)*sq_run;
+    }
+    const uint32_t nb = B->nb = ue - u0;
+    B->rbase.assign(Q.wb.begin() + R.wb0 + (u0 - R.u0), Q.wb.begin() + R.wb0 + (ue - R.u0) + 1);
+    B->uh.assign(run_uh->begin() + (u0 - R.u0), run_uh->begin() + (ue - R.u0));
+    B->uflags = Q.uflags.p + u0;
+    if (fb.units.grow(nb) || fb.rbase.grow(nb + 1)) return fail(OVL_ERR_OOM, "unit buffers");
+    HIPC(hipMemcpyAsync(fb.units.p, units.data() + u0, sizeof(Unit) * nb, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(fb.rbase.p, B->rbase.data(), 8ull * (nb + 1), hipMemcpyHostToDevice, s));
+    return OVL_OK;
+  }
+
+  // Chaining.  The batch is cut to the hit budget (plan_chain); *nc units are chained.  The first
+  // launch chains every unit whose targets fit one pass of the 128-target table and lists the
+  // others; the second chains the listed units over several passes with a done set sized for
+  // their targets.  Capacities come from the probe's hit counts; a batch that still overflows
+  // one (the counters say by how much) is chained again with bigger buffers -- never dropped.
+  int chain_batch(const ProbedBatch &B, uint32_t *nc, uint32_t *npairs, uint32_t *nnodes) {
+    auto &fb = c->fb;
+    const uint32_t hash_reads = c->hash_end_iid - c->hash_bgn_iid + 1;
+    auto plan = [&]() {
+      return plan_chain(B.uh.data(), B.nb, B.rbase.data(), hit_budget, per_unit, chain_waves,
+                        OVL_NODE_BLOCK, win_cap);
+    };
+    ChainPlan P = plan();
+    bool planned = true;               // P is new: its live list is not uploaded yet
+    uint32_t hc[16];
+    for (int attempt = 0;; attempt++) {
+      if (P.pool_cap >= 0xFFFFFFF0ull || P.pairs_cap >= 0xFFFFFFF0ull || P.pnodes_cap >= 0xFFFFFFF0ull)
+        return fail(OVL_ERR_UNSUPPORTED, "chain buffers past 2^32 entries (%llu hits)",
+                    (unsigned long long)P.hsum);
+      // sized for the hit budget, not this batch's hits: the next batch reuses them as they are
+      if (fb.pool.grow(std::max(P.pool_cap, chain_pool_for(hit_budget, chain_waves, OVL_NODE_BLOCK))) ||
+          fb.pnodes.grow(std::max<uint64_t>(P.pnodes_cap, hit_budget + 1)) || fb.pairs.grow(P.pairs_cap) ||
+          fb.big.grow(P.nc) || fb.chits.grow(1)) {
+        if (P.nc == 1 || P.hsum <= (16ull << 20))
+          return fail(OVL_ERR_OOM, "chain buffers (%llu hits)", (unsigned long long)P.hsum);
+        hit_budget = P.hsum / 2;                         // fewer units per chain launch
+        // the buffers that did fit were sized for the larger budget: drop them too
+        fb.pool.release();
+        fb.pnodes.release();
+        fb.pairs.release();
+        P = plan();
+        planned = true;
+        attempt--;
+        continue;
+      }
+      if (planned && !P.all_live() && !P.live.empty()) {
+        if (fb.live.grow(P.live.size())) return fail(OVL_ERR_OOM, "unit list");
+        HIPC(hipMemcpyAsync(fb.live.p, P.live.data(), 4ull * P.live.size(), hipMemcpyHostToDevice, s));
+      }
+      planned = false;
+      uint32_t ctr_init[16] = {0};
+      ctr_init[1] = 1;                                 // pool_next: node 0 is null
+      HIPC(hipMemcpyAsync(fb.ctr.p, ctr_init, 64, hipMemcpyHostToDevice, s));
+      HIPC(hipMemsetAsync(fb.chits.p, 0, 8, s));
+      ChainArgs CA = {};             // no done set, no profile counters
+      CA.R = c->reads();
+      CA.occ = c->d_occ.p;
+      CA.units = fb.units.p;
+      CA.rbase = fb.rbase.p;
+      CA.probes = fb.probe.p;
+      CA.unit_flags = B.uflags;
+      CA.nunits = P.all_live() ? P.nc : (uint32_t)P.live.size();
+      CA.k = k;
+      CA.unit_next = fb.ctr.p + 0;
+      CA.pool = fb.pool.p;
+      CA.pool_next = fb.ctr.p + 1;
+      CA.pool_cap = (uint32_t)P.pool_cap;
+      CA.pnodes = fb.pnodes.p;
+      CA.pnodes_next = fb.ctr.p + 2;
+      CA.pnodes_cap = (uint32_t)P.pnodes_cap;
+      CA.pairs = fb.pairs.p;
+      CA.npairs = fb.ctr.p + 3;
+      CA.pairs_cap = (uint32_t)P.pairs_cap;
+      CA.overflow = fb.ctr.p + 4;
+      CA.unit_list = P.all_live() ? nullptr : fb.live.p;
+      CA.big_units = fb.big.p;
+      CA.n_big = fb.ctr.p + 10;
+      CA.seed_hits = fb.chits.p;
+#ifdef OVL_CHAIN_PROF
+      if (!c->dbg.p) {
+        if (c->dbg.alloc(32)) return fail(OVL_ERR_OOM, "debug counters");
+        HIPC(hipMemsetAsync(c->dbg.p, 0, 256, s));
+      }
+      CA.prof = c->dbg.p + 24;
+#endif
+      HIPC(hipEventRecord(c->ev[4], s));
+      hipLaunchKernelGGL(k_chain, dim3(chain_waves / 4), dim3(256), 0, s, CA);
+      HIPC(hipGetLastError());
+      HIPC(hipMemcpyAsync(hc, fb.ctr.p, 64, hipMemcpyDeviceToHost, s));
+      HIPC(hipStreamSynchronize(s));
+      const uint32_t n_big = hc[10];
+      if (n_big && !hc[4]) {
+        std::vector<uint32_t> big(n_big);
+        HIPC(hipMemcpy(big.data(), fb.big.p, 4ull * n_big, hipMemcpyDeviceToHost));
+        uint32_t cap = 1;                              // distinct targets of any listed unit
+        for (uint32_t b : big) cap = std::max<uint32_t>(cap, std::min<uint32_t>(B.uh[b], hash_reads));
+        uint32_t smask = 1;
+        while (smask + 1 < 2ull * cap) smask = 2 * smask + 1;
+        uint32_t w2 = std::min<uint32_t>(chain_waves, (n_big + 3) & ~3u);
+        while (w2 > 4 && (uint64_t)w2 * (cap + smask + 1) * 4 > (4ull << 30)) w2 = (w2 / 2 + 3) & ~3u;
+        if (fb.done.grow((size_t)w2 * cap) || fb.dset.grow((size_t)w2 * (smask + 1)))
+          return fail(OVL_ERR_OOM, "done sets (%u targets x %u waves)", cap, w2);
+        HIPC(hipMemsetAsync(fb.dset.p, 0, 4ull * w2 * (smask + 1), s));
+        HIPC(hipMemsetAsync(fb.ctr.p, 0, 4, s));      // unit_next
+        CA.unit_list = fb.big.p;
+        CA.nunits = n_big;
+        CA.big_units = nullptr;
+        CA.n_big = nullptr;
+        CA.done_slots = fb.done.p;
+        CA.done_set = fb.dset.p;
+        CA.done_cap = cap;
+        CA.set_mask = smask;
+        hipLaunchKernelGGL(k_chain, dim3(w2 / 4), dim3(256), 0, s, CA);
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(hc, fb.ctr.p, 64, hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        c->stats.multi_pass_units += n_big;
+      }
+      HIPC(hipEventRecord(c->ev[5], s));
+      HIPC(hipStreamSynchronize(s));
+      if (!hc[4]) break;
+      if ((hc[4] & 4u) || attempt >= 3)
+        return fail(OVL_ERR_HIP, "chain capacity still exceeded after %d attempts (flags %u)",
+                    attempt + 1, hc[4]);
+      // grow what overflowed from what the counters asked for, then chain the batch again
+      if (hc[4] & 1u) P.pool_cap = (uint64_t)hc[1] + (uint64_t)(chain_waves + 2) * OVL_NODE_BLOCK;
+      if (hc[4] & 2u) {
+        P.pairs_cap = std::max<uint64_t>(P.pairs_cap, (uint64_t)hc[3] + 1024);
+        P.pnodes_cap = std::max<uint64_t>(P.pnodes_cap, (uint64_t)hc[2] + 1024);
+      }
+      c->stats.chain_retries++;
+    }
+    win_budget = P.win_budget;
+    float t = 0;
+    (void)hipEventElapsedTime(&t, c->ev[4], c->ev[5]);
+    c->stats.ms_seed += t;
+    unsigned long long h = 0;
+    HIPC(hipMemcpy(&h, fb.chits.p, 8, hipMemcpyDeviceToHost));
+    c->stats.seed_hits += h;
+    c->stats.pairs += hc[3];
+    c->stats.seed_nodes += hc[2];                        // pnodes_next: the lists' nodes
+    *nc = P.nc;
+    *npairs = hc[3];
+    *nnodes = hc[2];
+    return OVL_OK;
+  }
+
+  // The extension kernels' device counters and the launch plan's figures into the context's
+  // ovl_stats (the steps add their own as they go).  Counters add up over the driver's hash
+  // batches (the reference sums its per-thread counters into globals, Process_Overlaps.C:156-163).
+  int add_stats() {
+    unsigned long long hs[16];
+    HIPC(hipMemcpy(hs, c->fb.stats.p, 128, hipMemcpyDeviceToHost));
+#ifdef OVL_CHAIN_PROF
+    if (c->dbg.p) {
+      unsigned long long cp[8];
+      (void)hipMemcpy(cp, c->dbg.p + 24, 64, hipMemcpyDeviceToHost);
+      const double tot = (double)(cp[0] + cp[1] + cp[2] + cp[3] + cp[4] + cp[5]) + 1e-9;
+      fprintf(stderr, "OVL_CHAIN_PROF wave-cycles (cumulative): probe+qualify %.3f stage %.3f "
+              "discover %.3f scatter %.3f replay %.3f emit %.3f (shares); %llu chunks, %llu "
+              "staged occurrences, %.0f cycles per chunk\n", cp[0] / tot, cp[1] / tot,
+              cp[2] / tot, cp[3] / tot, cp[4] / tot, cp[5] / tot, cp[6], cp[7],
+              tot / (double)(cp[6] ? cp[6] : 1));
+    }
+#endif
+    if (c->dbg.p) {
+      unsigned long long dd[32];
+      (void)hipMemcpy(dd, c->dbg.p, 256, hipMemcpyDeviceToHost);
+      fprintf(stderr, "OVL_DEBUG cyc_A=%llu cyc_B=%llu cyc_cont=%llu cyc_C=%llu cyc_argmax=%llu "
+              "cyc_remove=%llu nodes=%llu\n", dd[16], dd[17], dd[18], dd[19], dd[20], dd[21],
+              dd[22]);
+      fprintf(stderr, "OVL_DEBUG ped=%llu rows=%llu chunks=%llu slide_iters=%llu tb=%llu iters=%llu "
+              "cyc_chunks=%llu cyc_tb=%llu pairs=%llu maxrows=%llu cyc_rest=%llu cyc_ped=%llu "
+              "cyc_calls=%llu cyc_pair=%llu cyc_stage=%llu cyc_extend=%llu\n",
+              dd[0], dd[1], dd[2], dd[3], dd[4], dd[5], dd[6], dd[7], dd[8], dd[9], dd[10], dd[11],
+              dd[12], dd[13], dd[14], dd[15]);
+    }
+    ovl_stats &S = c->stats;
+    S.kmer_hits_without_olap += hs[0];
+    S.kmer_hits_with_olap += hs[1];
+    S.kmer_hits_skipped += hs[2];
+    S.multi_overlaps += hs[3];
+    S.total_overlaps += hs[4];
+    S.contained_overlaps += hs[5];
+    S.dovetail_overlaps += hs[6];
+    S.bad_short_window += hs[8];
+    S.bad_long_window += hs[9];
+    // the read-length cap of the first staged launch, and of the last when there are several
+    // (the wide class, always last, shares its predecessor's)
+    const size_t ns = ext.stage.size() - (!ext.stage.empty() && ext.stage.back().wide);
+    S.ext_waves = ns ? ext.stage[0].waves : 0;
+    S.generic_waves = ext.gen.waves;
+    S.stage_len = ns ? ext.stage[0].len : 0;
+    S.long_stage_len = ns > 1 ? ext.stage[ns - 1].len : 0;
+    return OVL_OK;
+  }
+};
+
 // Process_Overlaps (overlapInCore-Process_Overlaps.C:101-137) over ref reads bgn..end of
 // libraries [lib_lo, lib_hi] against the current index.  append: keep the records and
 // counters already held (the driver's later hash batches).
@@ -1720,8 +2589,6 @@ static int find_impl(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, ui
   if (!c) return fail(OVL_ERR_STATE, "null context");
   if (!c->have_index) return fail(OVL_ERR_STATE, "ovl_build_hash_index() first");
   HIPC(hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const uint32_t k = c->P.kmer_len;
   if (bgn < 1) bgn = 1;
   if (bgn < c->first_iid) bgn = c->first_iid;
   uint32_t last = c->first_iid + c->nreads - 1;
@@ -1731,20 +2598,14 @@ static int find_impl(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, ui
   std::vector<Unit> units;
   std::vector<uint64_t> uwin;
   uint64_t nref = 0;
-  for (uint32_t a = bgn; a <= end && a >= bgn; a++) {
-    uint32_t r = a - c->first_iid;
-    int32_t L = (int32_t)c->h_len[r];
-    uint32_t lib = read_lib(c, r);
-    if (lib < lib_lo || lib > lib_hi) continue;  // -R (Process_Overlaps.C:108)
-    if (L < c->P.min_olap_len) continue;         // :114
-    nref++;
-    if (L < (int32_t)k) continue;
-    if (a >= c->hash_end_iid) continue;          // no hash read with a larger ID
-    units.push_back(Unit{r, 0});
-    units.push_back(Unit{r, 1});
-    uwin.push_back((uint64_t)(L - (int32_t)k + 1));
-    uwin.push_back((uint64_t)(L - (int32_t)k + 1));
-  }
+  query_rule(c, lib_lo, lib_hi).each(bgn, end, [&](uint32_t a, bool ref, uint64_t w) {
+    nref += ref;
+    if (!w || a >= c->hash_end_iid) return;        // no hash read with a larger ID
+    for (uint32_t dir = 0; dir < 2; dir++) {
+      units.push_back(Unit{a - c->first_iid, dir});
+      uwin.push_back(w);
+    }
+  });
   if (!append) {
     c->acc.nu = c->acc.nn = c->acc.np = 0;          // a new job: nothing pending
     ovl_stats keep_idx = c->stats;
@@ -1767,969 +2628,49 @@ static int find_impl(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, ui
       return fail(OVL_ERR_HIP, "sorted query windows: unit list mismatch");
     Q.probed = -1;                                  // a new index: no run probed against it
   }
+
+  FindRun run{c, c->stream, c->P.kmer_len, c->P.frag_olap_limit != UINT64_MAX,
+              c->P.use_window_filter && c->P.max_erate <= 0.06};
+  if (run.window && !c->have_qual)
+    return fail(OVL_ERR_BAD_PARAM, "-w (window filter) needs the reads' qualities");
+  if (int rc = run.begin(units.size())) return rc;
+
+  const uint32_t nu = (uint32_t)units.size();
+  const bool bloom = nu > 0 && use_bloom(c, bgn, end);
   std::vector<uint32_t> sq_uh;                      // the probed run's unit hit counts
   size_t sq_run = 0;
-
-  // per-context device buffers, sized per batch
-  // A batch is sized by seed hits (node pool + list-ordered copy: 32 B per hit); the probe
-  // window budget adapts to the hits-per-window ratio seen so far so that a batch's probe
-  // results are all consumed (units beyond the hit budget would otherwise be re-probed).
-  // seed hits per batch; halved while the chain buffers do not fit the HBM the index
-  // leaves, as the probe-slot cap is for the probe records
-  // 3.5 G: the 50k x 10 kb job in 2 chunks (1.27 s per step) rather than 4 (1.29 s) or 8
-  // (1.34 s) -- fewer re-probed windows and extension tails; node indices stay < 2^32
-  uint64_t HIT_BUDGET = 3584ull << 20;
-  {
-    // within the HBM left beside the index: the node pool and its list-ordered copy take
-    // ~33 B per hit; keep them under 60 % of what is free now plus what they already hold
-    size_t fr = 0, tot = 0;
-    if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
-      const uint64_t held = (c->fb.pool.n + c->fb.pnodes[0].n + c->fb.pnodes[1].n) * sizeof(Node);
-      HIT_BUDGET = std::min<uint64_t>(HIT_BUDGET, (uint64_t)((fr + held) * 0.6) / 33);
-    }
-    // a driver job's later searches chain within the buffers its first one sized (more hit
-    // chunks per run instead of a regrow of the pool and its copy)
-    if (c->sticky_budgets && c->fb.pnodes[0].n > (16ull << 20))
-      HIT_BUDGET = std::min<uint64_t>(HIT_BUDGET, c->fb.pnodes[0].n - 1);
-  }
-  if (const char *e = getenv("OVL_HIT_BUDGET_M"))             // experiments: millions of hits
-    HIT_BUDGET = std::max<uint64_t>(16, strtoull(e, nullptr, 10)) << 20;
-  HIT_BUDGET = std::max<uint64_t>(HIT_BUDGET, 16ull << 20);
-  uint64_t win_cap = 1536ull << 20;
-  uint64_t WIN_BUDGET = 512ull << 20;           // probe slots per batch (8 B each)
-  auto &d_rbase = c->fb.rbase;
-  auto &d_probe = c->fb.probe;
-  auto &d_uhits = c->fb.uhits;
-  auto &d_uflags = c->fb.uflags;
-  auto &d_ctr = c->fb.ctr;
-  auto &d_defer = c->fb.defer;
-  auto &d_pool = c->fb.pool;
-  auto &d_stats = c->fb.stats;
-  // OVL_PIPELINE=1 runs chunk i's extension on a second stream while chunk i+1 is probed and
-  // chained (two buffer slots).  Measured slower (50k x 10 kb: 1.37-1.41 s vs 1.31 s per
-  // job): the extension keeps every CU's issue slots busy, so the co-running probe and chain
-  // only take them from it.  Default: one stream, one slot.
-  // -l: every pair through the ordered generic kernel (a unit's pairs one after another)
-  const bool ordered = c->P.frag_olap_limit != UINT64_MAX;
-  const bool pipe = getenv("OVL_PIPELINE") != nullptr && !ordered;
-  hipStream_t xs = pipe ? c->xstream : s;
-  const bool window = c->P.use_window_filter && c->P.max_erate <= 0.06;
-  if (window && !c->have_qual)
-    return fail(OVL_ERR_BAD_PARAM, "-w (window filter) needs the reads' qualities");
-  if (d_ctr.alloc(16) || d_stats.alloc(16) || c->fb.xctr[0].alloc(16) ||
-      c->fb.xctr[1].alloc(16) || c->fb.xnout.alloc(1))
-    return fail(OVL_ERR_OOM, "counters");
-  HIPC(hipMemsetAsync(d_stats.p, 0, 128, s));
-
-  // ---- extension configuration --------------------------------------------------------
-  // Pairs go through up to three launches: the staged kernel at full occupancy (8 waves per
-  // <= 64 KB block) for pairs whose reads are both <= len1, the staged kernel with more LDS
-  // per wave for reads <= len2, and the generic kernel for the rest (reads with an 'n',
-  // bands wider than the register window, longer reads).  Each launch's scratch and LDS are
-  // sized for its own length class, so one long read in a job does not shrink the others.
-  auto ecap_of = [&](uint64_t L) {
-    return c->h_error_bound[std::min<uint64_t>(L, AS_MAX_READLEN)] + 2;
-  };
-  auto sw_of = [](uint64_t L) { return (int32_t)(((L + 31) / 32 + 2) & ~1ull); };
-  // per wave: the two strands' plane words, the scratch and the pair-state block
-  auto stg_lds_of = [&](uint64_t L) {
-    return 4ull * (4ull * (uint64_t)sw_of(L) + OVL_SCR_STAGE + OVL_STATE_INTS);
-  };
-  auto ml_of = [](int32_t ec) { return 4ull * (((uint64_t)(ec + 2) + 3) & ~3ull); };
-  // the staged kernel's block-shared Edit_Match_Limit table
-  auto sml_of = [&](int32_t ec) { return ml_of(ec); };
-  auto fits = [&](uint64_t L, uint32_t wpb, size_t cap) {
-    return stg_lds_of(L) * wpb + sml_of(ecap_of(L)) <= cap;
-  };
-  auto longest_fitting = [&](uint32_t wpb, size_t cap) -> uint32_t {
-    uint64_t lo = 0, hi = c->max_len;
-    if (fits(hi, wpb, cap)) return (uint32_t)hi;
-    while (lo + 1 < hi) {
-      const uint64_t mid = (lo + hi) / 2;
-      if (fits(mid, wpb, cap)) lo = mid; else hi = mid;
-    }
-    return (uint32_t)lo;
-  };
-  struct ExtClass {
-    uint32_t len = 0, wpb = 1, waves = 0;
-    int32_t ecap = 0, sw = 0;
-    size_t lds = 0;
-    bool l16 = false;
-    uint64_t stride = 0;
-    bool wide = false;             // the 2 x OVL_RJ-chunk register window (wide bands)
-  };
-  // the staged kernel instance of a class
-  auto stage_kernel = [](bool l16, bool wide) -> const void * {
-    if (wide) return l16 ? reinterpret_cast<const void *>(k_extend<true, true, false, 2 * OVL_RJ>)
-                         : reinterpret_cast<const void *>(k_extend<true, false, false, 2 * OVL_RJ>);
-    return l16 ? reinterpret_cast<const void *>(k_extend<true, true>)
-               : reinterpret_cast<const void *>(k_extend<true, false>);
-  };
-  const uint64_t SCRATCH_BUDGET = 24ull << 30;
-  std::vector<ExtClass> ext_stage;
-  auto per_wave_bytes = [](const ExtClass &g) {
-    return g.stride * 4 + 16ull * (g.ecap + 2) + 28ull * (g.ecap + 8);
-  };
-  auto make_stage = [&](uint32_t L, size_t cap, bool allow_knob, bool wide = false) -> int {
-    ExtClass g;
-    g.len = L;
-    g.wide = wide;
-    g.ecap = ecap_of(L);
-    g.sw = sw_of(L);
-    g.l16 = L < 16384;
-    g.wpb = (uint32_t)std::min<uint64_t>(8, (cap - std::min<uint64_t>(cap, sml_of(g.ecap))) / stg_lds_of(L));
-    if (g.wpb < 1) return -1;
-    g.lds = stg_lds_of(L) * g.wpb + sml_of(g.ecap);
-    // experiment knob: OVL_EXT_BLOCKS_PER_CU pads the LDS so that at most that many blocks
-    // fit on a CU (occupancy studies); unset = natural occupancy
-    if (allow_knob)
-      if (const char *bp = getenv("OVL_EXT_BLOCKS_PER_CU")) {
-        int nb = atoi(bp);
-        if (nb > 0) g.lds = std::max<size_t>(g.lds, (160 * 1024) / nb - 256);
-      }
-    const uint64_t lw = wide ? std::max<uint64_t>(OVL_LOGW, 128 * OVL_RJ) : OVL_LOGW;
-    uint64_t st = (uint64_t)(g.ecap + 2) * lw / (g.l16 ? 2 : 1);   // the row log
-    if (window) st = std::max<uint64_t>(st, 3ull * (g.ecap + 9) + 2ull * L + 64);
-    g.stride = (st + 63) & ~63ull;
-    const void *kfn = stage_kernel(g.l16, wide);
-    if (g.lds > 64 * 1024)
-      if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds) != hipSuccess)
-        return -1;
-    // persistent grid: as many blocks as are resident at once (registers and LDS), so no
-    // block starts only after the work queue has drained; within the scratch budget
-    uint32_t waves = 4u * OVL_EXT_OCC * c->n_cu;
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, kfn, 64 * g.wpb, g.lds) == hipSuccess &&
-        bpc > 0)
-      waves = std::min<uint32_t>(waves, (uint32_t)bpc * g.wpb * c->n_cu);
-    while (waves > g.wpb && (uint64_t)waves * per_wave_bytes(g) > SCRATCH_BUDGET) waves /= 2;
-    g.waves = std::max<uint32_t>(g.wpb, (waves / g.wpb) * g.wpb);
-    if (!wide) c->ext_classes.push_back(g.len);
-    ext_stage.push_back(g);
-    return 0;
-  };
-  c->ext_classes.clear();
-  // occupancy tiers of the staged kernel: 3 blocks of 8 waves per CU (the register limit),
-  // 3 blocks of 6, then blocks of up to 8 waves within 160 KB (as many as fit a CU).  A
-  // class's length is the span it stages (k_extend stages a pair's overlap span, not its
-  // whole reads): the tier's limit, or the longest loaded read when that is shorter, so a
-  // short-read job's launch is exactly what it was and a long-read job's pairs with shorter
-  // spans run at the higher occupancy.
-  {
-    uint32_t prev = 0;
-    const size_t tier_cap[3] = {52 * 1024, 52 * 1024, 160 * 1024};
-    const uint32_t tier_wpb[3] = {8, 6, 1};
-    for (int t = 0; t < 3; t++) {
-      const uint32_t T = longest_fitting(tier_wpb[t], tier_cap[t]);
-      const uint32_t L = std::min<uint32_t>(T, c->max_len);
-      if (L < 64 || L <= prev) continue;
-      if (make_stage(L, tier_cap[t], t == 0)) return fail(OVL_ERR_HIP, "staged kernel setup");
-      prev = L;
-    }
-    // the wide class: the pairs of every staged class whose band outgrew the register window
-    // (the rest of their deferrals -- 'n' bases -- pass on to the generic kernel)
-    if (!ext_stage.empty() && !getenv("OVL_NO_WIDE") &&
-        make_stage(ext_stage.back().len, 160 * 1024, false, true))
-      return fail(OVL_ERR_HIP, "wide staged kernel setup");
-  }
-  // the generic kernel: every read length; rows in LDS while two row buffers and the
-  // Edit_Match_Limit table fit a CU, else in global memory (GR)
-  ExtClass gen;
-  gen.len = c->max_len;
-  gen.ecap = ecap_of(c->max_len);
-  {
-    const size_t ml = ml_of(gen.ecap);
-    size_t w = 4ull * ((2ull * (2 * gen.ecap + 8) + TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3ull);
-    gen.l16 = w + ml > 160 * 1024;                       // GR
-    if (gen.l16) w = 4ull * ((TB_ROWS * TB_W + OVL_LDCAP + OVL_STATE_INTS + 3) & ~3ull);
-    gen.wpb = (4 * w <= 80 * 1024) ? 4 : (2 * w <= 80 * 1024) ? 2 : 1;
-    gen.lds = w * gen.wpb + (gen.l16 ? 0 : ml);
-    uint64_t st = (uint64_t)(gen.ecap + 2) * (gen.ecap + 2) + 4ull * (gen.ecap + 2) + 64;
-    if (window) st = std::max<uint64_t>(st, 3ull * (gen.ecap + 9) + 2ull * c->max_len + 64);
-    // a wave's band-compact row log holds every row of one extension (quadratic in the
-    // error limit); past 2^28 ints the GR kernel checks its cursor and fails loudly
-    if (gen.l16) st = std::min<uint64_t>(st, 1ull << 28);
-    gen.stride = (st + 63) & ~63ull;
-    uint32_t waves = 24u * c->n_cu;
-    while (waves > gen.wpb && (uint64_t)waves * per_wave_bytes(gen) > (16ull << 30)) waves /= 2;
-    gen.waves = std::max<uint32_t>(gen.wpb, (waves / gen.wpb) * gen.wpb);
-    const void *kfn = gen.l16 ? reinterpret_cast<const void *>(k_extend<false, true>)
-                              : reinterpret_cast<const void *>(k_extend<false, false>);
-    if (ordered)
-      kfn = gen.l16 ? reinterpret_cast<const void *>(k_extend<false, true, true>)
-                    : reinterpret_cast<const void *>(k_extend<false, false, true>);
-    if (gen.lds > 64 * 1024)
-      HIPC(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen.lds));
-  }
-  uint64_t rows_n = gen.stride * gen.waves, rowdir_n = 4ull * (gen.ecap + 2) * gen.waves,
-           deltas_n = 7ull * (gen.ecap + 8) * gen.waves;
-  for (const ExtClass &g : ext_stage) {
-    rows_n = std::max<uint64_t>(rows_n, g.stride * g.waves);
-    rowdir_n = std::max<uint64_t>(rowdir_n, 4ull * (g.ecap + 2) * g.waves);
-    deltas_n = std::max<uint64_t>(deltas_n, 7ull * (g.ecap + 8) * g.waves);
-  }
-  auto &d_rows = c->fb.rows;
-  auto &d_rowdir = c->fb.rowdir;
-  auto &d_deltas = c->fb.deltas;
-  if (d_rows.alloc(rows_n) || d_rowdir.alloc(rowdir_n) || d_deltas.alloc(deltas_n))
-    return fail(OVL_ERR_OOM, "extension scratch");
-  c->stats_ext_waves = ext_stage.empty() ? 0 : ext_stage[0].waves;
-  c->stats_gen_waves = gen.waves;
-  uint32_t chain_waves = 4u * OVL_CHAIN_OCC * c->n_cu;   // OVL_CHAIN_OCC blocks of 4 waves per CU
-
-  // With OVL_PIPELINE, chunk i's extension runs on xs while chunk i+1 is probed and chained
-  // on s.  Any return from here on first drains xs (its kernels use this context's buffers).
-  struct Drain {
-    hipStream_t x;
-    ~Drain() { (void)hipStreamSynchronize(x); }
-  } drain{xs};
-  // records: the device counter xnout continues from the records already held (the
-  // driver's earlier hash batches); the host tracks an upper bound (<= 3 per pair)
-  uint32_t nout32 = (uint32_t)c->nout;
-  HIPC(hipMemcpyAsync(c->fb.xnout.p, &nout32, 4, hipMemcpyHostToDevice, s));
-  HIPC(hipStreamSynchronize(s));
-  uint64_t nout_ub = c->nout;
-  auto ensure_out = [&](uint64_t need) -> int {
-    if (need <= c->d_out.n && c->d_out.p) return OVL_OK;
-    HIPC(hipStreamSynchronize(xs));
-    uint32_t cur = 0;
-    HIPC(hipMemcpy(&cur, c->fb.xnout.p, 4, hipMemcpyDeviceToHost));
-    DBuf<Rec> bigger;
-    if (bigger.alloc(need + (need >> 2))) return fail(OVL_ERR_OOM, "output grow");
-    if (cur)
-      HIPC(hipMemcpyAsync(bigger.p, c->d_out.p, sizeof(Rec) * cur, hipMemcpyDeviceToDevice, s));
-    HIPC(hipStreamSynchronize(s));
-    std::swap(bigger.p, c->d_out.p);
-    std::swap(bigger.n, c->d_out.n);
-    return OVL_OK;
-  };
-  if (int rc = ensure_out(std::max<uint64_t>(c->nout + (1u << 20), c->nout + units.size() * 8)))
-    return rc;
-
-  float ms_probe = 0, ms_chain = 0, ms_ext = 0;
-  float ms_probe_rest = 0;        // the sorted-window probe step's work beside its kernel
-  uint64_t npairs_tot = 0, probe_bytes = 0, seed_hits_tot = 0, n_big_units = 0, nodes_tot = 0;
-  uint64_t staged_pairs = 0, long_pairs = 0, generic_pairs = 0;
-  uint32_t chain_retries = 0;
-  uint32_t n_probe_launch = 0, n_ext_launch = 0, n_probe_sorted = 0;
-  uint32_t nu = (uint32_t)units.size();
-  uint32_t u0 = 0;
-  const uint32_t ctr_next[4] = {5, 11, 13, 15}, ctr_defer[4] = {8, 12, 14, 10};
-  bool pending[2] = {false, false};
-  uint32_t slot_pairs[2] = {0, 0};
-  // chunk i's extension has finished: its counters, class split and time
-  auto collect = [&](int sl) -> int {
-    if (!pending[sl]) return OVL_OK;
-    pending[sl] = false;
-    HIPC(hipEventSynchronize(c->xev[2 + sl]));
-    uint32_t hx[16];
-    HIPC(hipMemcpy(hx, c->fb.xctr[sl].p, 64, hipMemcpyDeviceToHost));
-    float t = 0;
-    (void)hipEventElapsedTime(&t, c->xev[sl], c->xev[2 + sl]);
-    ms_ext += t;
-    if (hx[7] & 32u)
-      return fail(OVL_ERR_UNSUPPORTED, "an extension needs more than 2^28 row cells (error limit "
-                  "%d of a %u-base read): past the generic kernel's per-wave row log",
-                  ecap_of(c->max_len), c->max_len);
-    if (hx[7]) return fail(OVL_ERR_HIP, "extension capacity exceeded (flags %u)", hx[7]);
-    uint32_t left = slot_pairs[sl];
-    for (size_t ci = 0; ci < ext_stage.size() && !ordered; ci++) {
-      const uint32_t nd = hx[ctr_defer[ci]];
-      if (getenv("OVL_DEBUG"))
-        fprintf(stderr, "OVL_DEBUG class %zu (reads <= %u): deferred %u of %u pairs\n", ci,
-                ext_stage[ci].len, nd, left);
-      if (ci == 0) staged_pairs += left - nd;
-      else long_pairs += left - nd;
-      left = nd;
-    }
-    generic_pairs += left;
-    return OVL_OK;
-  };
-  // One chunk's (or the accumulator's) pairs through the extension kernels on xs, the host
-  // not waiting: work order, the staged classes, the generic kernel; collect(slot) reads
-  // its counters back.
-  auto launch_ext = [&](int slot, const Unit *ext_units, PairRec *ext_pairs, Node *ext_pnodes,
-                        uint32_t npairs, uint32_t nc) -> int {
-    auto &x_ctr = c->fb.xctr[slot];
-      nout_ub += 3ull * npairs;
-      if (int rc = ensure_out(nout_ub)) return rc;
-      ExtendArgs EA;
-      EA.R = c->reads();
-      EA.units = ext_units;
-      EA.pairs = ext_pairs;
-      EA.npairs = npairs;
-      EA.npairs_dev = nullptr;
-      EA.restore = 0;
-      EA.pnodes = ext_pnodes;
-      EA.pair_next = x_ctr.p + 5;
-      EA.error_bound = c->d_error_bound.p;
-      EA.match_limit = c->d_match_limit.p;
-      EA.max_errors = c->max_errors;
-      EA.branch_match_value = c->branch_match_value;
-      EA.min_branch_tail_slope = c->min_branch_tail_slope;
-      EA.min_branch_end_dist = 20;
-      EA.partial = c->P.partial;
-      EA.unique = c->P.unique_olap_per_pair;
-      EA.min_olap_len = c->P.min_olap_len;
-      EA.use_hopeless = c->P.use_hopeless_check;
-      EA.k = (int32_t)k;
-      EA.filter_by_kmer_count = c->P.filter_by_kmer_count;
-      EA.minkmer_exp = exp(-1.0 * (double)k * c->P.max_erate);
-      EA.rows = d_rows.p;
-      EA.rowdir = d_rowdir.p;
-      EA.deltas = d_deltas.p;
-      EA.out = c->d_out.p;
-      EA.nout = c->fb.xnout.p;
-      EA.out_cap = (uint32_t)std::min<uint64_t>(c->d_out.n, 0xFFFFFFF0ull);
-      EA.stats = d_stats.p;
-      EA.window = window ? 1 : 0;
-      EA.overflow = x_ctr.p + 7;
-      EA.dbg = nullptr;
-      if (getenv("OVL_DEBUG")) {
-        if (!c->dbg.p) {
-          HIPC(hipStreamSynchronize(xs));
-          if (c->dbg.alloc(32)) return fail(OVL_ERR_OOM, "debug counters");
-          HIPC(hipMemsetAsync(c->dbg.p, 0, 256, xs));
-        }
-        EA.dbg = c->dbg.p;
-      }
-      EA.list = nullptr;
-      EA.defer = nullptr;
-      EA.ndefer = nullptr;
-      EA.olim = c->P.frag_olap_limit;
-      EA.nunits = nc;
-      EA.useg = nullptr;
-      EA.ord_slot = nullptr;
-      EA.ord_diag = nullptr;
-      EA.dkey = nullptr;
-      slot_pairs[slot] = npairs;
-      HIPC(hipMemsetAsync(x_ctr.p, 0, 64, xs));
-      if (npairs && ordered) {
-        // the reference's two pair orders per unit (see k_olim_keys): String_Olap_Space
-        // order and By_Diag_Sum order, by stable radix sorts
-        auto &fb = c->fb;
-        const int n = (int)npairs;
-        size_t t1 = 0, t2 = 0, t3 = 0;
-        HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, t1, fb.okey.p, fb.okey2.p, fb.oa.p,
-                                                fb.ob.p, n, 0, 32, xs));
-        HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, t2, fb.ok64a.p, fb.ok64b.p, fb.oa.p,
-                                                fb.ob.p, n, 0, 64, xs));
-        HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, t3, fb.ucnt.p, fb.useg.p, (int)nc + 1, xs));
-        const size_t tmp = std::max(std::max(t1, t2), t3);
-        HIPC(hipStreamSynchronize(xs));
-        if (fb.okey.grow(npairs) || fb.okey2.grow(npairs) || fb.oa.grow(npairs) ||
-            fb.ob.grow(npairs) || fb.oidx.grow(npairs) || fb.oidx2.grow(npairs) ||
-            fb.ok64a.grow(npairs) || fb.ok64b.grow(npairs) || fb.dkey.grow(npairs) ||
-            fb.ucnt.grow((size_t)nc + 1) || fb.useg.grow((size_t)nc + 1) ||
-            fb.otmp.grow(std::max<size_t>(tmp, 1)))
-          return fail(OVL_ERR_OOM, "-l pair orders");
-        const dim3 grid(std::min<uint32_t>((npairs + 255) / 256, 4096)), blk(256);
-        HIPC(hipMemsetAsync(fb.ucnt.p, 0, 4ull * (nc + 1), xs));
-        // first-hit order: by ~tgt, then (stably) by (unit, diag_bgn)
-        hipLaunchKernelGGL(k_olim_keys, grid, blk, 0, xs, ext_pairs, ext_pnodes, npairs, (int32_t)k,
-                           fb.okey.p, fb.ok64a.p, fb.oa.p, fb.dkey.p, fb.ucnt.p);
-        HIPC(hipGetLastError());
-        HIPC(hipcub::DeviceScan::ExclusiveSum(fb.otmp.p, t3, fb.ucnt.p, fb.useg.p, (int)nc + 1, xs));
-        size_t tt = t1;
-        HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.okey.p, fb.okey2.p, fb.oa.p,
-                                                fb.ob.p, n, 0, 32, xs));
-        hipLaunchKernelGGL(k_gather_u64, grid, blk, 0, xs, fb.ok64a.p, fb.ob.p, npairs, fb.ok64b.p);
-        tt = t2;
-        HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.ok64b.p, fb.ok64a.p, fb.ob.p,
-                                                fb.oa.p, n, 0, 64, xs));
-        // String_Olap_Space indices, then the order by (unit, index)
-        hipLaunchKernelGGL(k_olim_slots, dim3(std::min<uint32_t>((nc + 3) / 4, 8192)), blk, 0, xs,
-                           ext_pairs, fb.oa.p, fb.useg.p, nc,
-                           c->first_iid - c->hash_bgn_iid, fb.ok64b.p, fb.ob.p);
-        HIPC(hipGetLastError());
-        tt = t2;
-        HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.ok64b.p, fb.ok64a.p, fb.ob.p,
-                                                fb.oidx.p, n, 0, 64, xs));       // oidx: ord_slot
-        // By_Diag_Sum: stably by the diagonal key, then stably by unit
-        hipLaunchKernelGGL(k_gather_u64, grid, blk, 0, xs, fb.dkey.p, fb.oidx.p, npairs, fb.ok64a.p);
-        tt = t2;
-        HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.ok64a.p, fb.ok64b.p, fb.oidx.p,
-                                                fb.oa.p, n, 0, 64, xs));
-        hipLaunchKernelGGL(k_gather_unit, grid, blk, 0, xs, ext_pairs, fb.oa.p, npairs, fb.okey.p);
-        tt = t1;
-        HIPC(hipcub::DeviceRadixSort::SortPairs(fb.otmp.p, tt, fb.okey.p, fb.okey2.p, fb.oa.p,
-                                                fb.oidx2.p, n, 0, 32, xs));      // oidx2: ord_diag
-        HIPC(hipGetLastError());
-        EA.useg = fb.useg.p;
-        EA.ord_slot = fb.oidx.p;
-        EA.ord_diag = fb.oidx2.p;
-        EA.dkey = fb.dkey.p;
-      }
-      if (npairs && !ordered) {
-        // the extension-only buffers are shared by the slots: regrowing one waits for xs
-        auto &fb = c->fb;
-        size_t tmp = 0;
-        HIPC(hipcub::DeviceRadixSort::SortPairsDescending(nullptr, tmp, fb.okey.p, fb.okey2.p,
-                                                          fb.oidx.p, fb.oidx2.p, (int)npairs, 0,
-                                                          32, xs));
-        if (fb.okey.n < npairs || fb.oidx.n < npairs || fb.okey2.n < npairs || fb.oidx2.n < npairs ||
-            d_defer.n < npairs || fb.defer2.n < npairs || fb.otmp.n < tmp || !fb.otmp.p) {
-          HIPC(hipStreamSynchronize(xs));
-          if (fb.okey.grow(npairs) || fb.oidx.grow(npairs) || fb.okey2.grow(npairs) ||
-              fb.oidx2.grow(npairs) || d_defer.grow(npairs) || fb.defer2.grow(npairs) ||
-              fb.otmp.grow(std::max<size_t>(tmp, 1)))
-            return fail(OVL_ERR_OOM, "work order");
-        }
-        if (npairs > 1) {
-          // longest-first work order (node count descending; ties keep pair order)
-          hipLaunchKernelGGL(k_pair_order_keys, dim3(std::min<uint32_t>((npairs + 255) / 256, 4096)),
-                             dim3(256), 0, xs, ext_pairs, npairs, fb.okey.p, fb.oidx.p);
-          HIPC(hipGetLastError());
-          HIPC(hipcub::DeviceRadixSort::SortPairsDescending(fb.otmp.p, tmp, fb.okey.p, fb.okey2.p,
-                                                            fb.oidx.p, fb.oidx2.p, (int)npairs, 0,
-                                                            32, xs));
-          EA.list = fb.oidx2.p;
-        }
-      }
-      HIPC(hipEventRecord(c->xev[slot], xs));
-      if (npairs && ordered) {
-        EA.e_cap = gen.ecap;
-        EA.rows_cap = gen.stride;
-        EA.sw_words = 0;
-        EA.pair_next = x_ctr.p + 9;
-        n_ext_launch++;
-        if (gen.l16)
-          hipLaunchKernelGGL((k_extend<false, true, true>), dim3(gen.waves / gen.wpb),
-                             dim3(64 * gen.wpb), gen.lds, xs, EA);
-        else
-          hipLaunchKernelGGL((k_extend<false, false, true>), dim3(gen.waves / gen.wpb),
-                             dim3(64 * gen.wpb), gen.lds, xs, EA);
-        HIPC(hipGetLastError());
-      } else if (npairs) {
-        // the staged classes in turn, each deferring what it cannot take to the next list
-        // (whose length the next launch reads from the device counter); the generic kernel
-        // takes the last list, or every pair when no class exists
-        uint32_t *defer_buf[2] = {d_defer.p, c->fb.defer2.p};
-        for (size_t ci = 0; ci < ext_stage.size(); ci++) {
-          const ExtClass &g = ext_stage[ci];
-          EA.e_cap = g.ecap;
-          EA.rows_cap = g.stride;
-          EA.sw_words = g.sw;
-          EA.pair_next = x_ctr.p + ctr_next[ci];
-          EA.defer = defer_buf[ci & 1];
-          EA.ndefer = x_ctr.p + ctr_defer[ci];
-          // without the pipeline, a later class whose input list is empty is not launched
-          // (the host reads the previous class's defer count, as for the generic kernel
-          // below): the bench job's one staged launch then is the extension's only launch
-          bool launch = true;
-          if (!pipe && ci > 0) {
-            uint32_t nd = 0;
-            HIPC(hipMemcpyAsync(&nd, x_ctr.p + ctr_defer[ci - 1], 4, hipMemcpyDeviceToHost, xs));
-            HIPC(hipStreamSynchronize(xs));
-            launch = nd > 0;
-          }
-          if (!launch) {
-            // an empty class defers nothing: its counter stays 0 for the next one
-          } else {
-          n_ext_launch++;
-          if (g.wide && g.l16)
-            hipLaunchKernelGGL((k_extend<true, true, false, 2 * OVL_RJ>), dim3(g.waves / g.wpb),
-                               dim3(64 * g.wpb), g.lds, xs, EA);
-          else if (g.wide)
-            hipLaunchKernelGGL((k_extend<true, false, false, 2 * OVL_RJ>), dim3(g.waves / g.wpb),
-                               dim3(64 * g.wpb), g.lds, xs, EA);
-          else if (g.l16)
-            hipLaunchKernelGGL((k_extend<true, true>), dim3(g.waves / g.wpb), dim3(64 * g.wpb), g.lds, xs, EA);
-          else
-            hipLaunchKernelGGL((k_extend<true, false>), dim3(g.waves / g.wpb), dim3(64 * g.wpb), g.lds, xs, EA);
-          HIPC(hipGetLastError());
-          }
-          EA.list = defer_buf[ci & 1];
-          EA.npairs_dev = x_ctr.p + ctr_defer[ci];
-          EA.restore = 1;          // a deferred pair may have had nodes removed (~Len)
-        }
-        EA.e_cap = gen.ecap;
-        EA.rows_cap = gen.stride;
-        EA.sw_words = 0;
-        EA.pair_next = x_ctr.p + 9;
-        EA.defer = nullptr;
-        EA.ndefer = nullptr;
-        // without the pipeline the host waits for this chunk next anyway: read the last
-        // class's defer count and skip an empty generic launch
-        bool gen_needed = true;
-        if (!pipe && !ext_stage.empty()) {
-          uint32_t nd = 0;
-          HIPC(hipMemcpyAsync(&nd, x_ctr.p + ctr_defer[ext_stage.size() - 1], 4,
-                              hipMemcpyDeviceToHost, xs));
-          HIPC(hipStreamSynchronize(xs));
-          gen_needed = nd > 0;
-        }
-        if (gen_needed) {
-          n_ext_launch++;
-          if (gen.l16)
-            hipLaunchKernelGGL((k_extend<false, true>), dim3(gen.waves / gen.wpb), dim3(64 * gen.wpb),
-                               gen.lds, xs, EA);
-          else
-            hipLaunchKernelGGL((k_extend<false, false>), dim3(gen.waves / gen.wpb), dim3(64 * gen.wpb),
-                               gen.lds, xs, EA);
-          HIPC(hipGetLastError());
-        }
-      }
-    HIPC(hipEventRecord(c->xev[2 + slot], xs));
-    pending[slot] = true;
-    return OVL_OK;
-  };
-  // Extend everything the accumulator holds; it is empty again for the next chunk (the
-  // stream orders the next appends after this launch's reads).
-  auto flush_acc = [&]() -> int {
-    if (int rc = collect(0)) return rc;
-    auto &A = c->acc;
-    const uint32_t np = (uint32_t)A.np;
-    slot_pairs[0] = np;
-    int rc = launch_ext(0, A.units.p, A.pairs.p, A.pnodes.p, np, (uint32_t)A.nu);
-    A.nu = A.nn = A.np = 0;
-    return rc;
-  };
-  // Append a chunk's units, list nodes and pairs to the accumulator (device copies on s,
-  // which the extension also runs on without OVL_PIPELINE: nothing is overwritten early).
-  const uint64_t ACC_PAIRS = 4ull << 20, ACC_NODES = 1ull << 30;
-  auto acc_append = [&](const Unit *u, uint32_t nu_c, const Node *nodes, uint64_t nn_c,
-                        const PairRec *pairs, uint32_t np_c) -> int {
-    auto &A = c->acc;
-    if (A.nu + nu_c >= 0xFFFFFFF0ull || A.nn + nn_c >= 0xFFFFFFF0ull)
-      return fail(OVL_ERR_UNSUPPORTED, "extension accumulator past 2^32 entries");
-    auto acc_fits = [&]() {
-      return A.units.n >= A.nu + nu_c && A.pnodes.n >= A.nn + nn_c && A.pairs.n >= A.np + np_c;
-    };
-    // once it holds a launch's worth (a quarter of the flush thresholds), what the
-    // accumulator holds is extended rather than moved into bigger buffers: a regrow on a full
-    // device costs ~1 s (the full-size configs[4] job, r05e), while smaller launches lose to
-    // their tails (one launch per search: extension 8.4 -> 23 s, r05f)
-    if (!acc_fits() && (A.np >= ACC_PAIRS / 4 || A.nn >= ACC_NODES / 4))
-      if (int rc = flush_acc()) return rc;
-    if (!acc_fits()) {
-      // growing moves the buffers: the pending extension (which reads them) must be done,
-      // and what the accumulator holds is carried over
-      HIPC(hipStreamSynchronize(xs));
-      HIPC(hipStreamSynchronize(s));
-      auto regrow = [&](auto &buf, uint64_t used, uint64_t need) -> int {
-        if (buf.n >= need && buf.p) return OVL_OK;
-        typename std::remove_reference<decltype(buf)>::type bigger;
-        if (bigger.alloc(std::max<uint64_t>(need, buf.n + buf.n / 2))) return -1;
-        if (used) HIPC(hipMemcpy(bigger.p, buf.p, used * sizeof(*buf.p), hipMemcpyDeviceToDevice));
-        std::swap(bigger.p, buf.p);
-        std::swap(bigger.n, buf.n);
-        return OVL_OK;
-      };
-      if (regrow(A.units, A.nu, A.nu + nu_c) || regrow(A.pnodes, A.nn, A.nn + nn_c) ||
-          regrow(A.pairs, A.np, A.np + np_c)) {
-        // no room for bigger buffers beside the ones being copied (a device nearly full of
-        // sorted windows, index and search buffers): what the accumulator holds is extended
-        // now, and the emptied buffers are freed before this chunk's own are allocated
-        if (A.nu || A.nn || A.np) {
-          if (int rc = flush_acc()) return rc;
-          HIPC(hipStreamSynchronize(xs));
-          HIPC(hipStreamSynchronize(s));
-        }
-        if ((A.units.n < nu_c && A.units.alloc(nu_c)) ||
-            (A.pnodes.n < nn_c && A.pnodes.alloc(nn_c)) || (A.pairs.n < np_c && A.pairs.alloc(np_c)))
-          return fail(OVL_ERR_OOM, "extension accumulator (%llu nodes)", (unsigned long long)nn_c);
-      }
-    }
-    if (nu_c)
-      HIPC(hipMemcpyAsync(A.units.p + A.nu, u, sizeof(Unit) * nu_c, hipMemcpyDeviceToDevice, s));
-    if (nn_c)
-      HIPC(hipMemcpyAsync(A.pnodes.p + A.nn, nodes, sizeof(Node) * nn_c, hipMemcpyDeviceToDevice, s));
-    if (np_c) {
-      hipLaunchKernelGGL(k_append_pairs, dim3(std::min<uint32_t>((np_c + 255) / 256, 4096)),
-                         dim3(256), 0, s, pairs, np_c, (uint32_t)A.nu, (uint32_t)A.nn,
-                         A.pairs.p + A.np);
-      HIPC(hipGetLastError());
-    }
-    A.nu += nu_c;
-    A.nn += nn_c;
-    A.np += np_c;
-    return OVL_OK;
-  };
-  const bool bloom = nu > 0 && use_bloom(c, bgn, end);
-  uint64_t chunk = 0;
-  while (u0 < nu) {
-    const int slot = pipe ? (int)(chunk & 1) : 0;
-    // this slot's buffers are free once the extension of chunk i-2 has finished
-    if (int rc = collect(slot)) return rc;
-    auto &d_units = c->fb.units[slot];
-    auto &d_pnodes = c->fb.pnodes[slot];
-    auto &d_pairs = c->fb.pairs[slot];
-    uint32_t nb = 0;
-    std::vector<uint64_t> rbase;
-    std::vector<uint32_t> uh;
-    uint32_t *chain_uflags = nullptr;
-    if (sqm) {
-      // the run of sorted windows holding unit u0: probed once per batch (k_probe_sorted),
-      // its records then chained in hit-budget chunks
-      auto &Q = c->sq;
-      while (Q.runs[sq_run].u1 <= u0) sq_run++;
-      const auto &R = Q.runs[sq_run];
-      const uint32_t ue = std::min<uint32_t>(R.u1, nu);
-      if (Q.probed != (int)sq_run) {
-        const uint64_t wlim = Q.wb[R.wb0 + (ue - R.u0)];
-        if (d_probe.grow(R.n)) return fail(OVL_ERR_OOM, "probe records (%llu)", (unsigned long long)R.n);
-        HIPC(hipEventRecord(c->ev[4], s));           // the probe step: seed-phase time
-        HIPC(hipMemsetAsync(d_probe.p, 0, 8ull * wlim, s));
-        HIPC(hipMemsetAsync(Q.uflags.p + R.u0, 0, 4ull * (ue - R.u0), s));
-        HIPC(hipMemsetAsync(Q.uhits.p + R.u0, 0, 4ull * (ue - R.u0), s));
-        SqProbeArgs SA;
-        SA.X = index_dev(c);
-        if (c->bloom_ok && sq_bloom()) {        // the filter in front of the table
-          SA.X.bloom = c->d_bloom.p;
-          SA.X.bloom_w = c->bloom_w;
-        }
-        SA.R = c->reads();
-        SA.key = Q.key.p + R.e0;
-        SA.wid = Q.wid.p + R.e0;
-        SA.n = R.n;
-        SA.wlim = (uint32_t)wlim;
-        SA.units = Q.dunits.p + R.u0;
-        SA.wbase = Q.dwbase.p + R.wb0;
-        SA.ublk = Q.ublk.p + R.ub0;
-        SA.k = k;
-        SA.out = d_probe.p;
-        SA.unit_flags = Q.uflags.p + R.u0;
-        SA.unit_hits = Q.uhits.p + R.u0;
-        // the kernel alone is timed (the records' zeroing and the unit hit counts around it
-        // are not the probe's bytes)
-        HIPC(hipEventRecord(c->ev[2], s));
-        hipLaunchKernelGGL(k_probe_sorted, dim3(8 * c->n_cu), dim3(256), 0, s, SA);
-        HIPC(hipEventRecord(c->ev[3], s));
-        n_probe_launch++;
-        n_probe_sorted++;
-        HIPC(hipGetLastError());
-        HIPC(hipEventRecord(c->ev[5], s));
-        sq_uh.resize(ue - R.u0);
-        HIPC(hipMemcpyAsync(sq_uh.data(), Q.uhits.p + R.u0, 4ull * (ue - R.u0),
-                            hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
-        float t = 0, tstep = 0;
-        (void)hipEventElapsedTime(&t, c->ev[2], c->ev[3]);
-        (void)hipEventElapsedTime(&tstep, c->ev[4], c->ev[5]);
-        ms_probe += t;
-        ms_probe_rest += tstep > t ? tstep - t : 0.f;  // the records' zeroing
-        // algorithmic bytes: the sorted windows (8-B key + 4-B id), and the table and its
-        // filter read once each -- or, when they are larger than the run (a full-size
-        // configs[4] super-batch's 68.7 GB table against a run of 2^29 windows), at most one
-        // entry and one filter word per window (the hits' 8-B records are not counted)
-        const uint64_t tab_b = 16ull << c->tab_bits;
-        const uint64_t flt_b = SA.X.bloom ? 8ull * ((1ull << (c->tab_bits - c->slice_bits)) << c->bloom_w) : 0ull;
-        probe_bytes += 12ull * R.n + std::min<uint64_t>(tab_b, 16ull * R.n) +
-                       std::min<uint64_t>(flt_b, 8ull * R.n);
-        Q.probed = (int)sq_run;
-      }
-      nb = ue - u0;
-      rbase.assign(Q.wb.begin() + R.wb0 + (u0 - R.u0), Q.wb.begin() + R.wb0 + (ue - R.u0) + 1);
-      uh.assign(sq_uh.begin() + (u0 - R.u0), sq_uh.begin() + (ue - R.u0));
-      chain_uflags = Q.uflags.p + u0;
-      if (d_units.grow(nb) || d_rbase.grow(nb + 1))
-        return fail(OVL_ERR_OOM, "unit buffers");
-      HIPC(hipMemcpyAsync(d_units.p, units.data() + u0, sizeof(Unit) * nb, hipMemcpyHostToDevice, s));
-      HIPC(hipMemcpyAsync(d_rbase.p, rbase.data(), 8ull * (nb + 1), hipMemcpyHostToDevice, s));
-    } else {
-    // batch by probe slots
-    uint32_t u1 = u0;
-    uint64_t wsum = 0;
-    while (u1 < nu && (wsum + uwin[u1] <= WIN_BUDGET || u1 == u0)) wsum += uwin[u1++];
-    nb = u1 - u0;
-    rbase.resize(nb + 1);
-    uint64_t acc = 0;
-    for (uint32_t i = 0; i < nb; i++) { rbase[i] = acc; acc += uwin[u0 + i]; }
-    rbase[nb] = acc;
-    if (d_units.grow(nb) || d_rbase.grow(nb + 1) || d_probe.grow(acc) ||
-        d_uhits.grow(nb) || d_uflags.grow(nb)) {
-      if (nb == 1 || WIN_BUDGET <= (16ull << 20)) return fail(OVL_ERR_OOM, "probe buffers");
-      win_cap = WIN_BUDGET = WIN_BUDGET / 2;
-      continue;
-    }
-    HIPC(hipMemcpyAsync(d_units.p, units.data() + u0, sizeof(Unit) * nb, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(d_rbase.p, rbase.data(), 8ull * (nb + 1), hipMemcpyHostToDevice, s));
-    ProbeArgs PA;
-    PA.R = c->reads();
-    PA.X = index_dev(c);
-    if (bloom) {
-      PA.X.bloom = c->d_bloom.p;
-      PA.X.bloom_w = c->bloom_w;
-    }
-    PA.units = d_units.p;
-    PA.rbase = d_rbase.p;
-    PA.nunits = nb;
-    PA.out = d_probe.p;
-    PA.unit_hits = d_uhits.p;
-    PA.unit_flags = d_uflags.p;
-    PA.k = k;
-    HIPC(hipEventRecord(c->ev[2], s));
-    if (bloom) hipLaunchKernelGGL(k_probe<true>, dim3((nb + 3) / 4), dim3(256), 0, s, PA);
-    else       hipLaunchKernelGGL(k_probe<false>, dim3((nb + 3) / 4), dim3(256), 0, s, PA);
-    n_probe_launch++;
-    HIPC(hipGetLastError());
-    HIPC(hipEventRecord(c->ev[3], s));
-    uh.resize(nb);
-    HIPC(hipMemcpyAsync(uh.data(), d_uhits.p, 4ull * nb, hipMemcpyDeviceToHost, s));
-    HIPC(hipStreamSynchronize(s));
-    float t = 0;
-    (void)hipEventElapsedTime(&t, c->ev[2], c->ev[3]);
-    ms_probe += t;
-    if (getenv("OVL_TIMING"))
-      fprintf(stderr, "OVL_TIMING probe launch: %u units, %llu windows, %.3f ms\n", nb,
-              (unsigned long long)acc, t);
-    // algorithmic bytes: per window one 16-B table entry and one 8-B Probe record, plus the
-    // packed query (2 bits per base); see DESIGN.md
-    probe_bytes += acc * 24 + acc / 4;
-    chain_uflags = d_uflags.p;
-    }
-    // shrink the batch to the hit budget (probe results stay valid for the prefix)
-    uint64_t hsum = 0;
-    uint32_t nc = 0;
-    auto fit_hits = [&]() {
-      hsum = 0;
-      nc = 0;
-      while (nc < nb && (hsum + uh[nc] <= HIT_BUDGET || nc == 0)) hsum += uh[nc++];
-      double ratio = (double)hsum / (double)std::max<uint64_t>(1, rbase[nc]);
-      double wb = (double)HIT_BUDGET / std::max(ratio, 1e-3) * 1.05;
-      WIN_BUDGET = (uint64_t)std::min(std::max(wb, 16.0 * (1 << 20)), (double)win_cap);
-    };
-    fit_hits();
-
-    // Chaining.  The first launch chains every unit whose targets fit one pass of the
-    // 128-target table and lists the others; the second chains the listed units over
-    // several passes with a done set sized for their targets.  Capacities come from the
-    // probe's hit counts; a batch that still overflows one (the counters say by how much)
-    // is chained again with bigger buffers -- never dropped.
-    uint64_t per_unit = 256;                           // test knob: force the regrow path
-    if (const char *e = getenv("OVL_TEST_PAIRS_PER_UNIT")) per_unit = std::max(1, atoi(e));
-    uint64_t pool_cap = 0, pairs_cap = 0, pnodes_cap = 0;
-    // nodes <= hits; a wave claims OVL_NODE_BLOCK nodes at a time for at most 64 lanes per
-    // claim, so a block wastes < 64 / 4096 of itself, and each wave ends holding one block
-    auto pool_for = [&](uint64_t h) {
-      return h + h / 32 + (uint64_t)(chain_waves + 2) * OVL_NODE_BLOCK + 8;
-    };
-    auto set_caps = [&]() {
-      pool_cap = pool_for(hsum);
-      pairs_cap = std::min<uint64_t>(hsum + 1, (uint64_t)nc * per_unit + 1024);
-      pnodes_cap = hsum + 1;
-    };
-    set_caps();
-    // only units with hits are chained: a unit without one adds no pair, node, counter or
-    // flag, yet its wave would read every window's record (a full-size configs[4] search
-    // against a super-batch of ~2 % of the reads: about half its units)
-    std::vector<uint32_t> live;
-    live.reserve(nc);
-    for (uint32_t i = 0; i < nc; i++)
-      if (uh[i]) live.push_back(i);
-    const bool all_live = live.size() == nc;
-    if (!all_live && !live.empty()) {
-      if (c->fb.live.grow(live.size())) return fail(OVL_ERR_OOM, "unit list");
-      HIPC(hipMemcpyAsync(c->fb.live.p, live.data(), 4ull * live.size(), hipMemcpyHostToDevice, s));
-    }
-    const uint32_t hash_reads = c->hash_end_iid - c->hash_bgn_iid + 1;
-    uint32_t hc[16];
-    unsigned long long chain_hits = 0;
-    for (int attempt = 0;; attempt++) {
-      if (pool_cap >= 0xFFFFFFF0ull || pairs_cap >= 0xFFFFFFF0ull || pnodes_cap >= 0xFFFFFFF0ull)
-        return fail(OVL_ERR_UNSUPPORTED, "chain buffers past 2^32 entries (%llu hits)",
-                    (unsigned long long)hsum);
-      // sized for the hit budget, not this batch's hits: the next batch reuses them as they are
-      if (d_pool.grow(std::max(pool_cap, pool_for(HIT_BUDGET))) ||
-          d_pnodes.grow(std::max<uint64_t>(pnodes_cap, HIT_BUDGET + 1)) || d_pairs.grow(pairs_cap) ||
-          c->fb.big.grow(nc) || c->fb.chits.grow(1)) {
-        if (nc == 1 || hsum <= (16ull << 20))
-          return fail(OVL_ERR_OOM, "chain buffers (%llu hits)", (unsigned long long)hsum);
-        HIT_BUDGET = hsum / 2;                         // fewer units per chain launch
-        // the buffers that did fit were sized for the larger budget: drop them too
-        d_pool.release();
-        d_pnodes.release();
-        d_pairs.release();
-        fit_hits();
-        set_caps();
-        attempt--;
-        continue;
-      }
-      uint32_t ctr_init[16] = {0};
-      ctr_init[1] = 1;                                 // pool_next: node 0 is null
-      HIPC(hipMemcpyAsync(d_ctr.p, ctr_init, 64, hipMemcpyHostToDevice, s));
-      HIPC(hipMemsetAsync(c->fb.chits.p, 0, 8, s));
-      ChainArgs CA;
-      CA.R = c->reads();
-      CA.occ = c->d_occ.p;
-      CA.units = d_units.p;
-      CA.rbase = d_rbase.p;
-      CA.probes = d_probe.p;
-      CA.unit_flags = chain_uflags;
-      CA.nunits = all_live ? nc : (uint32_t)live.size();
-      CA.k = k;
-      CA.unit_next = d_ctr.p + 0;
-      CA.pool = d_pool.p;
-      CA.pool_next = d_ctr.p + 1;
-      CA.pool_cap = (uint32_t)pool_cap;
-      CA.pnodes = d_pnodes.p;
-      CA.pnodes_next = d_ctr.p + 2;
-      CA.pnodes_cap = (uint32_t)pnodes_cap;
-      CA.pairs = d_pairs.p;
-      CA.npairs = d_ctr.p + 3;
-      CA.pairs_cap = (uint32_t)pairs_cap;
-      CA.overflow = d_ctr.p + 4;
-      CA.unit_list = all_live ? nullptr : c->fb.live.p;
-      CA.big_units = c->fb.big.p;
-      CA.n_big = d_ctr.p + 10;
-      CA.done_slots = nullptr;
-      CA.done_set = nullptr;
-      CA.done_cap = 0;
-      CA.set_mask = 0;
-      CA.seed_hits = c->fb.chits.p;
-      CA.prof = nullptr;
-#ifdef OVL_CHAIN_PROF
-      if (!c->dbg.p) {
-        if (c->dbg.alloc(32)) return fail(OVL_ERR_OOM, "debug counters");
-        HIPC(hipMemsetAsync(c->dbg.p, 0, 256, s));
-      }
-      CA.prof = c->dbg.p + 24;
-#endif
-      HIPC(hipEventRecord(c->ev[4], s));
-      hipLaunchKernelGGL(k_chain, dim3(chain_waves / 4), dim3(256), 0, s, CA);
-      HIPC(hipGetLastError());
-      HIPC(hipMemcpyAsync(hc, d_ctr.p, 64, hipMemcpyDeviceToHost, s));
-      HIPC(hipStreamSynchronize(s));
-      const uint32_t n_big = hc[10];
-      if (n_big && !hc[4]) {
-        std::vector<uint32_t> big(n_big);
-        HIPC(hipMemcpy(big.data(), c->fb.big.p, 4ull * n_big, hipMemcpyDeviceToHost));
-        uint32_t cap = 1;                              // distinct targets of any listed unit
-        for (uint32_t b : big) cap = std::max<uint32_t>(cap, std::min<uint32_t>(uh[b], hash_reads));
-        uint32_t smask = 1;
-        while (smask + 1 < 2ull * cap) smask = 2 * smask + 1;
-        uint32_t w2 = std::min<uint32_t>(chain_waves, (n_big + 3) & ~3u);
-        while (w2 > 4 && (uint64_t)w2 * (cap + smask + 1) * 4 > (4ull << 30)) w2 = (w2 / 2 + 3) & ~3u;
-        if (c->fb.done.grow((size_t)w2 * cap) || c->fb.dset.grow((size_t)w2 * (smask + 1)))
-          return fail(OVL_ERR_OOM, "done sets (%u targets x %u waves)", cap, w2);
-        HIPC(hipMemsetAsync(c->fb.dset.p, 0, 4ull * w2 * (smask + 1), s));
-        HIPC(hipMemsetAsync(d_ctr.p, 0, 4, s));      // unit_next
-        CA.unit_list = c->fb.big.p;
-        CA.nunits = n_big;
-        CA.big_units = nullptr;
-        CA.n_big = nullptr;
-        CA.done_slots = c->fb.done.p;
-        CA.done_set = c->fb.dset.p;
-        CA.done_cap = cap;
-        CA.set_mask = smask;
-        hipLaunchKernelGGL(k_chain, dim3(w2 / 4), dim3(256), 0, s, CA);
-        HIPC(hipGetLastError());
-        HIPC(hipMemcpyAsync(hc, d_ctr.p, 64, hipMemcpyDeviceToHost, s));
-        HIPC(hipStreamSynchronize(s));
-        n_big_units += n_big;
-      }
-      HIPC(hipEventRecord(c->ev[5], s));
-      HIPC(hipStreamSynchronize(s));
-      if (!hc[4]) break;
-      if ((hc[4] & 4u) || attempt >= 3)
-        return fail(OVL_ERR_HIP, "chain capacity still exceeded after %d attempts (flags %u)",
-                    attempt + 1, hc[4]);
-      // grow what overflowed from what the counters asked for, then chain the batch again
-      if (hc[4] & 1u) pool_cap = (uint64_t)hc[1] + (uint64_t)(chain_waves + 2) * OVL_NODE_BLOCK;
-      if (hc[4] & 2u) {
-        pairs_cap = std::max<uint64_t>(pairs_cap, (uint64_t)hc[3] + 1024);
-        pnodes_cap = std::max<uint64_t>(pnodes_cap, (uint64_t)hc[2] + 1024);
-      }
-      chain_retries++;
-    }
-    {
-      float t = 0;
-      (void)hipEventElapsedTime(&t, c->ev[4], c->ev[5]);
-      ms_chain += t;
-    }
-    {
-      unsigned long long h = 0;
-      HIPC(hipMemcpy(&h, c->fb.chits.p, 8, hipMemcpyDeviceToHost));
-      chain_hits += h;
-      seed_hits_tot += chain_hits;
-    }
-    uint32_t npairs = hc[3];
-    npairs_tot += npairs;
-    nodes_tot += hc[2];                                  // pnodes_next: the lists' nodes
-
-    // ---- the extension ----------------------------------------------------------------
-    // Default path: the chunk's chains go to the accumulator (c->acc) and are extended
-    // together once ACC_PAIRS pairs have gathered or the job ends, so a launch's tail (its
-    // last, longest pairs on few waves) is paid once per job rather than once per probe
-    // chunk and per hash batch (canu's small --hashbits batches made that tail most of a
-    // configs[4] rank's extension time).  -l (a unit's pairs in the reference's order) and
-    // OVL_PIPELINE extend each chunk as it comes, from the slot's own buffers.
-    if (!ordered && !pipe) {
-      if (int rc = acc_append(d_units.p, nc, d_pnodes.p, hc[2], d_pairs.p, npairs)) return rc;
+  for (uint32_t u0 = 0; u0 < nu;) {
+    // the search buffers are free once the extension launched from them has finished
+    if (int rc = run.collect_extension()) return rc;
+    ProbedBatch B;
+    if (int rc = sqm ? run.probe_sorted_run(units, u0, &sq_run, &sq_uh, &B)
+                     : run.probe_lookup(units, uwin, u0, bloom, &B))
+      return rc;
+    uint32_t nc = 0, npairs = 0, nnodes = 0;
+    if (int rc = run.chain_batch(B, &nc, &npairs, &nnodes)) return rc;
+    // The chunk's chains go to the accumulator (c->acc) and are extended together once
+    // ACC_PAIRS pairs have gathered or the job ends, so a launch's tail (its last, longest
+    // pairs on few waves) is paid once per job rather than once per probe chunk and per hash
+    // batch (canu's small --hashbits batches made that tail most of a configs[4] rank's
+    // extension time).  -l (a unit's pairs in the reference's order) extends each chunk as it
+    // comes, from the search buffers.
+    auto &fb = c->fb;
+    if (!run.ordered) {
+      if (int rc = run.acc_append(fb.units.p, nc, fb.pnodes.p, nnodes, fb.pairs.p, npairs)) return rc;
       if (c->acc.np >= ACC_PAIRS || c->acc.nn >= ACC_NODES)
-        if (int rc = flush_acc()) return rc;
+        if (int rc = run.flush_acc()) return rc;
     } else {
-      if (int rc = launch_ext(slot, d_units.p, d_pairs.p, d_pnodes.p, npairs, nc)) return rc;
+      if (int rc = run.launch_extension(fb.units.p, fb.pairs.p, fb.pnodes.p, npairs, nc)) return rc;
     }
-    chunk++;
     u0 += nc;
   }
   if (flush && c->acc.np)
-    if (int rc = flush_acc()) return rc;
-  for (int sl = 0; sl < 2; sl++)
-    if (int rc = collect(sl)) return rc;
-  {
-    uint32_t n = 0;
-    HIPC(hipMemcpy(&n, c->fb.xnout.p, 4, hipMemcpyDeviceToHost));
-    c->nout = n;
-  }
-  unsigned long long hs[16];
-  HIPC(hipMemcpy(hs, d_stats.p, 128, hipMemcpyDeviceToHost));
-#ifdef OVL_CHAIN_PROF
-  if (c->dbg.p) {
-    unsigned long long cp[8];
-    (void)hipMemcpy(cp, c->dbg.p + 24, 64, hipMemcpyDeviceToHost);
-    const double tot = (double)(cp[0] + cp[1] + cp[2] + cp[3] + cp[4] + cp[5]) + 1e-9;
-    fprintf(stderr, "OVL_CHAIN_PROF wave-cycles (cumulative): probe+qualify %.3f stage %.3f "
-            "discover %.3f scatter %.3f replay %.3f emit %.3f (shares); %llu chunks, %llu "
-            "staged occurrences, %.0f cycles per chunk\n", cp[0] / tot, cp[1] / tot,
-            cp[2] / tot, cp[3] / tot, cp[4] / tot, cp[5] / tot, cp[6], cp[7],
-            tot / (double)(cp[6] ? cp[6] : 1));
-  }
-#endif
-  if (c->dbg.p) {
-    unsigned long long dd[32];
-    (void)hipMemcpy(dd, c->dbg.p, 256, hipMemcpyDeviceToHost);
-    fprintf(stderr, "OVL_DEBUG cyc_A=%llu cyc_B=%llu cyc_cont=%llu cyc_C=%llu cyc_argmax=%llu "
-            "cyc_remove=%llu nodes=%llu\n", dd[16], dd[17], dd[18], dd[19], dd[20], dd[21],
-            dd[22]);
-    fprintf(stderr, "OVL_DEBUG ped=%llu rows=%llu chunks=%llu slide_iters=%llu tb=%llu iters=%llu "
-            "cyc_chunks=%llu cyc_tb=%llu pairs=%llu maxrows=%llu cyc_rest=%llu cyc_ped=%llu "
-            "cyc_calls=%llu cyc_pair=%llu cyc_stage=%llu cyc_extend=%llu\n",
-            dd[0], dd[1], dd[2], dd[3], dd[4], dd[5], dd[6], dd[7], dd[8], dd[9], dd[10], dd[11],
-            dd[12], dd[13], dd[14], dd[15]);
-  }
-  // counters add up over the driver's hash batches (the reference sums its per-thread
-  // counters into globals, Process_Overlaps.C:156-163)
-  c->stats.kmer_hits_without_olap += hs[0];
-  c->stats.kmer_hits_with_olap += hs[1];
-  c->stats.kmer_hits_skipped += hs[2];
-  c->stats.multi_overlaps += hs[3];
-  c->stats.total_overlaps += hs[4];
-  c->stats.contained_overlaps += hs[5];
-  c->stats.dovetail_overlaps += hs[6];
-  c->stats.seed_hits += seed_hits_tot;
-  c->stats.multi_pass_units += n_big_units;
-  c->stats.chain_retries += chain_retries;
-  c->stats.staged_pairs += staged_pairs;
-  c->stats.long_pairs += long_pairs;
-  c->stats.generic_pairs += generic_pairs;
-  c->stats.ext_waves = c->stats_ext_waves;
-  c->stats.generic_waves = c->stats_gen_waves;
-  c->stats.stage_len = c->ext_classes.empty() ? 0 : c->ext_classes[0];
-  c->stats.long_stage_len = c->ext_classes.size() > 1 ? c->ext_classes.back() : 0;
-  c->stats.bad_short_window += hs[8];
-  c->stats.bad_long_window += hs[9];
-  c->stats.pairs += npairs_tot;
-  c->stats.seed_nodes += nodes_tot;
-  c->stats.ms_seed += ms_probe + ms_probe_rest + ms_chain;
-  c->stats.ms_extend += ms_ext;
-  c->stats.ms_probe_kernel += ms_probe;
-  c->stats.probe_bytes += probe_bytes;
-  c->stats.probe_launches += n_probe_launch;
-  c->stats.probe_sorted_launches += n_probe_sorted;
-  c->stats.extend_launches += n_ext_launch;
+    if (int rc = run.flush_acc()) return rc;
+  if (int rc = run.collect_extension()) return rc;
+  uint32_t n = 0;
+  HIPC(hipMemcpy(&n, c->fb.xnout.p, 4, hipMemcpyDeviceToHost));
+  c->nout = n;
+  if (int rc = run.add_stats()) return rc;
   *n_out = c->nout;
   return OVL_OK;
 }
@@ -2747,15 +2688,12 @@ int ovl_seed_hits(ovl_ctx *c, uint32_t bgn, uint32_t end, ovl_seed_hit *out, uin
   if (end > last) end = last;
   std::vector<Unit> units;
   std::vector<uint64_t> uwin;
-  for (uint32_t a = bgn; a <= end && a >= bgn; a++) {
-    uint32_t r = a - c->first_iid;
-    int32_t L = (int32_t)c->h_len[r];
-    if (L < c->P.min_olap_len || L < (int32_t)k) continue;
-    units.push_back(Unit{r, 0});
-    units.push_back(Unit{r, 1});
-    uwin.push_back((uint64_t)(L - (int32_t)k + 1));
-    uwin.push_back((uint64_t)(L - (int32_t)k + 1));
-  }
+  query_rule(c).each(bgn, end, [&](uint32_t a, bool, uint64_t w) {
+    for (uint32_t dir = 0; w && dir < 2; dir++) {
+      units.push_back(Unit{a - c->first_iid, dir});
+      uwin.push_back(w);
+    }
+  });
   // units in batches of <= 512 M probe slots; each batch's hits are written to a device
   // buffer of at most 256 M hits (4 GB), in pieces of whole units
   const uint64_t WIN_BUDGET = 512ull << 20, HIT_BUF = 256ull << 20;
@@ -2767,35 +2705,16 @@ int ovl_seed_hits(ovl_ctx *c, uint32_t bgn, uint32_t end, ovl_seed_hit *out, uin
   float ms_tot = 0;
   const uint32_t nu = (uint32_t)units.size();
   for (uint32_t u0 = 0; u0 < nu;) {
-    uint32_t u1 = u0;
-    uint64_t acc = 0;
-    while (u1 < nu && (acc + uwin[u1] <= WIN_BUDGET || u1 == u0)) acc += uwin[u1++];
+    const uint32_t u1 = take_within(uwin, u0, nu, WIN_BUDGET);
     const uint32_t nb = u1 - u0;
-    std::vector<uint64_t> rbase(nb + 1);
-    acc = 0;
-    for (uint32_t i = 0; i < nb; i++) { rbase[i] = acc; acc += uwin[u0 + i]; }
-    rbase[nb] = acc;
-    if (fb.units[0].grow(nb) || fb.rbase.grow(nb + 1) || fb.probe.grow(acc) ||
-        fb.uhits.grow(nb) || fb.uflags.grow(nb) || ucnt.grow(nb) || ubase.grow(nb))
-      return fail(OVL_ERR_OOM, "seed-hit buffers");
-    HIPC(hipMemcpyAsync(fb.units[0].p, units.data() + u0, sizeof(Unit) * nb, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(fb.rbase.p, rbase.data(), 8ull * (nb + 1), hipMemcpyHostToDevice, s));
-    HIPC(hipEventRecord(c->ev[2], s));
-    ProbeArgs PA;
-    PA.R = c->reads();
-    PA.X = index_dev(c);
-    PA.units = fb.units[0].p;
-    PA.rbase = fb.rbase.p;
-    PA.nunits = nb;
-    PA.out = fb.probe.p;
-    PA.unit_hits = fb.uhits.p;
-    PA.unit_flags = fb.uflags.p;
-    PA.k = k;
-    hipLaunchKernelGGL(k_probe<false>, dim3((nb + 3) / 4), dim3(256), 0, s, PA);
+    std::vector<uint64_t> rbase;
+    if (ucnt.grow(nb) || ubase.grow(nb)) return fail(OVL_ERR_OOM, "seed-hit buffers");
+    if (int rc = probe_batch(c, units.data() + u0, uwin.data() + u0, nb, false, &rbase))
+      return rc == OVL_ERR_OOM ? fail(OVL_ERR_OOM, "seed-hit buffers") : rc;
     HitArgs HA;
     HA.R = c->reads();
     HA.occ = c->d_occ.p;
-    HA.units = fb.units[0].p;
+    HA.units = fb.units.p;
     HA.rbase = fb.rbase.p;
     HA.probes = fb.probe.p;
     HA.nunits = nb;
@@ -2823,13 +2742,11 @@ int ovl_seed_hits(ovl_ctx *c, uint32_t bgn, uint32_t end, ovl_seed_hit *out, uin
     std::vector<uint64_t> base(nb, 0);
     std::vector<uint32_t> cuts{0};
     uint64_t hmax = 1;
-    for (uint32_t p0 = 0; p0 < nb;) {
-      uint32_t p1 = p0;
+    for (uint32_t p0 = 0; p0 < nb; p0 = cuts.back()) {
       uint64_t h = 0;
-      while (p1 < nb && (h + cnt[p1] <= HIT_BUF || p1 == p0)) { base[p1] = h; h += cnt[p1++]; }
+      cuts.push_back(take_within(cnt, p0, nb, HIT_BUF, &h));
+      for (uint32_t i = p0 + 1; i < cuts.back(); i++) base[i] = base[i - 1] + cnt[i - 1];
       hmax = std::max<uint64_t>(hmax, h);
-      cuts.push_back(p1);
-      p0 = p1;
     }
     if (hbuf.grow(hmax))
       return fail(OVL_ERR_OOM, "seed-hit list (%llu hits)", (unsigned long long)hmax);
@@ -2838,7 +2755,7 @@ int ovl_seed_hits(ovl_ctx *c, uint32_t bgn, uint32_t end, ovl_seed_hit *out, uin
       const uint32_t p0 = cuts[pc], p1 = cuts[pc + 1];
       const uint64_t a2 = base[p1 - 1] + cnt[p1 - 1];
       HA.out = hbuf.p;
-      HA.units = fb.units[0].p + p0;
+      HA.units = fb.units.p + p0;
       HA.rbase = fb.rbase.p + p0;
       HA.unit_base = ubase.p + p0;
       HA.nunits = p1 - p0;
@@ -2880,7 +2797,6 @@ static std::vector<std::pair<uint32_t, uint32_t>> plan_query_chunks(ovl_ctx *c, 
                                                                     uint32_t lib_hi,
                                                                     uint64_t *max_windows) {
   std::vector<std::pair<uint32_t, uint32_t>> out;
-  const uint32_t k = c->P.kmer_len;
   size_t fr = 0, tot = 0;
   uint64_t budget = UINT64_MAX;
   if (hipMemGetInfo(&fr, &tot) == hipSuccess) {
@@ -2893,13 +2809,8 @@ static std::vector<std::pair<uint32_t, uint32_t>> plan_query_chunks(ovl_ctx *c, 
   wcap = std::max<uint64_t>(wcap, 1);
   uint32_t lo = bgn;
   uint64_t w = 0;
-  for (uint32_t a = bgn; a <= end && a >= bgn; a++) {
-    const uint32_t r = a - c->first_iid;
-    const int32_t L = (int32_t)c->h_len[r];
-    const uint32_t lib = read_lib(c, r);
-    uint64_t add = 0;
-    if (!(lib < lib_lo || lib > lib_hi || L < c->P.min_olap_len || L < (int32_t)k))
-      add = 2ull * (uint64_t)(L - (int32_t)k + 1);
+  query_rule(c, lib_lo, lib_hi).each(bgn, end, [&](uint32_t a, bool, uint64_t win) {
+    const uint64_t add = 2 * win;                    // both orientations
     if (w + add > wcap && a > lo) {
       out.push_back({lo, a - 1});
       *max_windows = std::max(*max_windows, w);
@@ -2907,7 +2818,7 @@ static std::vector<std::pair<uint32_t, uint32_t>> plan_query_chunks(ovl_ctx *c, 
       w = 0;
     }
     w += add;
-  }
+  });
   if (end >= bgn) out.push_back({lo, end});
   *max_windows = std::max(*max_windows, w);
   return out;
@@ -2917,12 +2828,7 @@ static std::vector<std::pair<uint32_t, uint32_t>> plan_query_chunks(ovl_ctx *c, 
 static uint64_t count_ref_reads(const ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo,
                                 uint32_t lib_hi) {
   uint64_t n = 0;
-  for (uint32_t a = bgn; a <= end && a >= bgn; a++) {
-    const uint32_t r = a - c->first_iid;
-    const uint32_t lib = read_lib(c, r);
-    if (lib < lib_lo || lib > lib_hi || (int32_t)c->h_len[r] < c->P.min_olap_len) continue;
-    n++;
-  }
+  query_rule(c, lib_lo, lib_hi).each(bgn, end, [&](uint32_t, bool ref, uint64_t) { n += ref; });
   return n;
 }
 
@@ -3136,13 +3042,8 @@ int ovl_overlap_driver(ovl_ctx *c, const ovl_driver_params *d, uint64_t *n_out) 
     // full-size configs[4] rank job (13.7 G windows, ~180 GB) does, its 1/8-scale side line
     // (3.8 G, ~50 GB) does not.  OVL_DENSE_TABLES=0|1 overrides.
     uint64_t qw = 0;
-    for (uint32_t a = g_bgn_ref; a <= ref_last && a >= g_bgn_ref; a++) {
-      const uint32_t r = a - c->first_iid;
-      const int32_t Lr = (int32_t)c->h_len[r];
-      const uint32_t lib = read_lib(c, r);
-      if (!(lib < d->min_lib_ref || lib > d->max_lib_ref || Lr < c->P.min_olap_len || Lr < (int32_t)k))
-        qw += 2ull * (uint64_t)(Lr - (int32_t)k + 1);
-    }
+    query_rule(c, d->min_lib_ref, d->max_lib_ref)
+        .each(g_bgn_ref, ref_last, [&](uint32_t, bool, uint64_t w) { qw += 2 * w; });
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) == hipSuccess) c->dense_tables = 13 * qw > tot / 4;
     if (const char *e = getenv("OVL_DENSE_TABLES")) c->dense_tables = atoi(e) != 0;

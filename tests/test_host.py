@@ -164,3 +164,23 @@ def test_c4_full_plan_covers_the_reads(monkeypatch):
     w = bench.Configs4Rank(bench.parse_args(["--workload", "configs4-rank", "--reads",
                                              "4000000"]), 7, 8, None)
     assert w.plan_jobs()[1]["h"] == js[7]["h"]
+
+
+def test_search_plan_header_under_sanitizers(tmp_path):
+    """tests/ovl_plan_check.cpp, a program of its own: the search's batch arithmetic
+    (canu_amd/csrc/ovl_plan.h -- the query-read rule, the budget cut, a chain launch's units,
+    live list and capacities, also after a budget halving) against hand-computed values,
+    under AddressSanitizer and UBSan."""
+    import os
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx = shutil.which(os.environ.get("CXX", "g++"))
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "ovl_plan_check")
+    subprocess.run([cxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-o", exe,
+                    os.path.join(root, "tests", "ovl_plan_check.cpp")], check=True, timeout=300)
+    cp = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert cp.returncode == 0, cp.stdout + cp.stderr
+    assert "ovl_plan_check ok" in cp.stdout
