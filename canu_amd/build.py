@@ -157,6 +157,47 @@ def build_emt_cli(force: bool = False, verbose: bool = True) -> str:
     return EMT_CLI_OUT
 
 
+PAIR_OUT = os.path.join(OUT_DIR, "libcanu_pair.so")
+PAIR_DEPS = [os.path.join(CSRC, "pair.hip"), os.path.join(HERE, "..", "include", "canu_pair.h"),
+             os.path.join(HERE, "..", "include", "canu_ovl.h")]
+PAIR_CLI_OUT = os.path.join(BIN_DIR, "overlapPair")
+
+
+def build_pair(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_pair.so: overlapPair, the exact realignment of MHAP overlaps."""
+    if not force and not _stale(PAIR_OUT, PAIR_DEPS):
+        return PAIR_OUT
+    os.makedirs(OUT_DIR, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, *HIPCC_FLAGS, "-o", PAIR_OUT + ".tmp", os.path.join(CSRC, "pair.hip")]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(PAIR_OUT + ".tmp", PAIR_OUT)
+    return PAIR_OUT
+
+
+def build_pair_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/overlapPair: the command line canu's mhap.sh runs after mhapConvert (host
+    C++ over libcanu_pair.so, found next to it through the rpath)."""
+    lib = build_pair(verbose=verbose)
+    src = os.path.join(CSRC, "pair_main.cpp")
+    deps = [src, lib, os.path.join(CSRC, "gkp_store.h"), os.path.join(CSRC, "ovl_ovb.h"),
+            os.path.join(CSRC, "ovb_reader.h"), *PAIR_DEPS[1:]]
+    if not force and not _stale(PAIR_CLI_OUT, deps):
+        return PAIR_CLI_OUT
+    os.makedirs(BIN_DIR, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
+           "-o", PAIR_CLI_OUT + ".tmp", src, "-L" + OUT_DIR, "-lcanu_pair",
+           "-Wl,-rpath,$ORIGIN/../lib", "-Wl,--allow-shlib-undefined"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(PAIR_CLI_OUT + ".tmp", PAIR_CLI_OUT)
+    return PAIR_CLI_OUT
+
+
 def build(force: bool = False, verbose: bool = True, profile: bool = False) -> str:
     """profile=True builds the instrumented variant (in-kernel cycle stamps, OVL_DEBUG=1
     prints them) as libcanu_ovl_prof.so; load it with CANU_OVL_LIB."""
@@ -182,3 +223,5 @@ if __name__ == "__main__":
         build_meryl(force="--force" in sys.argv)
         build_meryl_cli(force="--force" in sys.argv)
         build_emt_cli(force="--force" in sys.argv)
+        build_pair(force="--force" in sys.argv)
+        build_pair_cli(force="--force" in sys.argv)

@@ -1,0 +1,712 @@
+// pair.hip -- libcanu_pair.so: canu's overlapPair (src/overlapInCore/overlapPair.C) on gfx950.
+//
+// One wave owns one overlap and runs recomputeOverlaps (:346-662) on the device: up to 13
+// dependent edit-distance passes (edlibAlign, restated in include/canu_pair.h) with the hang
+// arithmetic between them, so nothing goes back to the host between passes.
+//
+// The DP is Myers' bit-vector recurrence (Myers 1999; the block step of edlib.C:276-330).
+// Lane b holds Pv/Mv of query rows 64b..64b+63 and the five match masks (A, C, G, T, N) of
+// those rows.  Columns run as a skewed wavefront: at step s lane b does column s-b and takes
+// the horizontal delta and the target base of that column from lane b-1 (one DPP wave_shr:1
+// of a packed word).  Lane 0 gets its base from a 64-column chunk of the target that the
+// wave loads coalesced and keeps in a register (v_readlane by the step), and its delta from
+// the top boundary (0 infix, +1 prefix/global) or, for a query of more than 4096 rows, from the
+// boundary row the previous stripe's last lane left: 2 bits per column, in LDS for targets
+// up to PAIR_LDS_COLUMNS, else in a per-wave global scratch row.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <vector>
+
+#include "../../include/canu_pair.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+#define HIP_TRY(x)                                                                      \
+  do {                                                                                  \
+    hipError_t e_ = (x);                                                                \
+    if (e_ != hipSuccess)                                                               \
+      return fail(e_ == hipErrorOutOfMemory ? PAIR_ERR_OOM : PAIR_ERR_HIP, "%s: %s", #x, \
+                  hipGetErrorString(e_));                                               \
+  } while (0)
+
+constexpr int WAVES_PER_BLOCK = 4;
+constexpr int LDS_WORDS = PAIR_LDS_COLUMNS / 16;      // boundary row of one wave, 2 bits/column
+constexpr int MHAP_SLOP = 500;                         // overlapPair.C:64
+constexpr uint32_t MAX_EVALUE = 4095;                  // AS_MAX_EVALUE, ovOverlap.H:42
+
+// per-overlap outcome bits, summed on the host into alignStats' counters
+enum : uint32_t {
+  F_SKIPPED = 1u << 0, F_PASSED = 1u << 1, F_FAILED = 1u << 2, F_FAILEXTA = 1u << 3,
+  F_FAILEXTB = 1u << 4, F_FAILEXT = 1u << 5, F_PARTIAL = 1u << 6, F_DOVETAIL = 1u << 7,
+  F_EXT5B = 1u << 8, F_EXT5A = 1u << 9, F_EXT3A = 1u << 10, F_EXT3B = 1u << 11
+};
+
+struct ReadTable {
+  const uint8_t *fwd;        // codes 0..3 = ACGT, 4 = N, read r at off[r]
+  const uint8_t *rc;         // the reverse complement of every read, same offsets
+  const uint64_t *off;
+  const uint32_t *len;
+  uint32_t first_iid, nreads;
+};
+
+// ------------------------------------------------------------------ read encoding
+
+__global__ void k_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
+                         const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ len,
+                         uint32_t nreads, uint8_t *__restrict__ fwd, uint8_t *__restrict__ rc,
+                         uint32_t *__restrict__ bad) {
+  for (uint32_t r = blockIdx.x; r < nreads; r += gridDim.x) {
+    const uint8_t *s = bases + src_off[r];
+    const uint64_t d = dst_off[r];
+    const uint32_t L = len[r];
+    for (uint32_t i = threadIdx.x; i < L; i += blockDim.x) {
+      const uint8_t ch = s[i];
+      uint8_t c = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
+      if (c == 4 && ch != 'N') atomicOr(bad, 1u);
+      fwd[d + i] = c;
+      rc[d + (L - 1 - i)] = c < 4 ? (uint8_t)(3 - c) : c;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ the aligner
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__device__ __forceinline__ int dpp_from_lower(int v, int lane0) {   // lane l <- v[l-1]
+  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xf, 0xf, false);
+}
+
+struct Seq {                 // a span of an oriented read, read forwards or backwards
+  const uint8_t *p;          // first base of the span
+  int n;
+  int rev;                   // element i is p[n-1-i]
+  __device__ __forceinline__ int at(int i) const { return p[rev ? n - 1 - i : i]; }
+};
+
+struct PassOut {
+  int best, bestcol;         // minimum of the bottom row, the first column attaining it
+  int lastcol;               // last column whose bottom-row score == want (-1: none)
+  int fin;                   // bottom-row score at the last column
+};
+
+// Bottom row of the edit-distance matrix of q (rows) against t (columns); top_hin 0 lets an
+// alignment start at any column (infix), 1 charges every skipped target base (prefix, global).
+// Needs q.n >= 1, t.n >= 1.  Every lane of the wave is in, with the same arguments.
+__device__ PassOut dp_pass(const Seq q, const Seq t, const int top_hin, const int want,
+                           uint32_t *lrow, uint32_t *grow, unsigned long long &steps) {
+  const int lane = threadIdx.x & 63;
+  const int m = q.n, n = t.n;
+  const int nstripes = (m + PAIR_STRIPE_ROWS - 1) / PAIR_STRIPE_ROWS;
+  const bool use_g = n > PAIR_LDS_COLUMNS;
+  int best = INT_MAX, bestcol = -1, lastcol = -1, sc = m;
+  int lb = 0;
+  for (int st = 0; st < nstripes; st++) {
+    const int r0 = st * PAIR_STRIPE_ROWS;
+    const int rows = min(PAIR_STRIPE_ROWS, m - r0);
+    const int nb = (rows + 63) >> 6;
+    const bool last = st == nstripes - 1;
+    lb = nb - 1;
+    // match masks: block c's 64 bases are loaded by the wave and balloted per letter
+    uint64_t pe0 = 0, pe1 = 0, pe2 = 0, pe3 = 0, pe4 = 0;
+    for (int c = 0; c < nb; c++) {
+      const int i = r0 + c * 64 + lane;
+      const int code = i < m ? q.at(i) : 7;
+      const uint64_t b0 = __ballot(code == 0), b1 = __ballot(code == 1),
+                     b2 = __ballot(code == 2), b3 = __ballot(code == 3),
+                     b4 = __ballot(code == 4);
+      if (lane == c) { pe0 = b0; pe1 = b1; pe2 = b2; pe3 = b3; pe4 = b4; }
+    }
+    uint64_t Pv = ~0ull, Mv = 0;
+    const bool trk = last && lane == lb;
+    const int rr = trk ? ((m - 1) & 63) : 63;
+    sc = m;
+    int x = 1;                                  // (hout + 1) | base << 2, handed to lane + 1
+    uint32_t cur = lane < n ? (uint32_t)t.at(lane) : 4u;
+    uint32_t nxt = 64 + lane < n ? (uint32_t)t.at(64 + lane) : 4u;
+    uint32_t hw = 0, acc = 0;
+    const int nsteps = n + nb - 1;
+    steps += (unsigned long long)nsteps;
+    for (int s = 0; s < nsteps; s++) {
+      if ((s & 63) == 0 && s > 0) {
+        cur = nxt;
+        const int c = s + 64 + lane;
+        nxt = c < n ? (uint32_t)t.at(c) : 4u;
+      }
+      const int base0 = __builtin_amdgcn_readlane((int)cur, s & 63);
+      int hin0 = top_hin;
+      if (st > 0) {
+        if ((s & 15) == 0 && s < n) hw = use_g ? grow[s >> 4] : lrow[s >> 4];
+        hin0 = (int)((hw >> (2 * (s & 15))) & 3u) - 1;
+      }
+      const int xin = dpp_from_lower(x, (hin0 + 1) | (base0 << 2));
+      const int j = s - lane;
+      const bool act = lane < nb && j >= 0 && j < n;
+      int d = 0;
+      if (act) {
+        const int hin = (xin & 3) - 1;
+        const int b = xin >> 2;
+        // the letter's match mask by bit selects (a chain of ?: compiles to branches)
+        const uint64_t s0 = 0 - (uint64_t)(b & 1), s1 = 0 - (uint64_t)((b >> 1) & 1),
+                       s2 = 0 - (uint64_t)(b >> 2);
+        const uint64_t e01 = (pe0 & ~s0) | (pe1 & s0), e23 = (pe2 & ~s0) | (pe3 & s0);
+        const uint64_t e03 = (e01 & ~s1) | (e23 & s1);
+        uint64_t Eq = (e03 & ~s2) | (pe4 & s2);
+        const uint64_t neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
+        const uint64_t Xv = Eq | Mv;
+        Eq |= neg;
+        const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
+        uint64_t Ph = Mv | ~(Xh | Pv);
+        uint64_t Mh = Pv & Xh;
+        d = (int)((Ph >> rr) & 1) - (int)((Mh >> rr) & 1);
+        Ph = (Ph << 1) | pos;
+        Mh = (Mh << 1) | neg;
+        Pv = Mh | ~(Xv | Ph);
+        Mv = Ph & Xv;
+        sc += d;
+        if (trk) {
+          if (sc < best) { best = sc; bestcol = j; }
+          if (sc == want) lastcol = j;
+        }
+        if (!last && lane == lb) {              // lane 63: the next stripe's top boundary
+          acc |= (uint32_t)(d + 1) << (2 * (j & 15));
+          if ((j & 15) == 15 || j == n - 1) {
+            if (use_g) grow[j >> 4] = acc; else lrow[j >> 4] = acc;
+            acc = 0;
+          }
+        }
+      }
+      x = (d + 1) | (xin & ~3);
+    }
+    if (!last) __threadfence();                 // lane 63's row is read by every lane next
+  }
+  PassOut o;
+  o.best = __shfl(best, lb);
+  o.bestcol = __shfl(bestcol, lb);
+  o.lastcol = __shfl(lastcol, lb);
+  o.fin = __shfl(sc, lb);
+  return o;
+}
+
+struct Oriented {            // an oriented read
+  const uint8_t *p;
+  int len;
+};
+
+struct WaveCtx {
+  uint32_t *lrow, *grow;
+  double erate;
+  unsigned long long cells;
+  unsigned long long steps;   // wavefront steps: columns + lanes - 1 per stripe
+  uint32_t passes;
+};
+
+__device__ __forceinline__ int max_edit(int a, int b, double erate) {
+  return (int)ceil(max(a, b) * erate * 1.1);
+}
+
+// extendAlignment (overlapPair.C:255-304): Q[qb,qe) is the query, T[tb,te) widened by slop
+// the target; on success tb/te move to the alignment found.
+__device__ bool extend_alignment(WaveCtx &w, const Oriented Q, int qb, int qe, const Oriented T,
+                                 int &tb, int &te, int slop, int &edit_dist, int &align_len) {
+  const int tbx = max(0, tb - slop);
+  const int tex = min(T.len, te + slop);
+  const int m = qe - qb, n = tex - tbx;
+  if (m <= 0 || n <= 0) return false;           // cannot happen with min_overlap_length >= 1
+  const int k = max_edit(m, n, w.erate);
+  const Seq q{Q.p + qb, m, 0};
+  const Seq t{T.p + tbx, n, 0};
+  PassOut f = dp_pass(q, t, 0, INT_MIN, w.lrow, w.grow, w.steps);
+  w.cells += (unsigned long long)m * n;
+  w.passes++;
+  const int best = uni(f.best), end = uni(f.bestcol);
+  if (best > k) return false;
+  // the start: prefix pass of the reversed query over the reversed target[0..end]; the
+  // last column still at `best` is the longest alignment (edlib.C:216-236)
+  const Seq qr{Q.p + qb, m, 1};
+  const Seq tr{T.p + tbx, end + 1, 1};
+  PassOut r = dp_pass(qr, tr, 1, best, w.lrow, w.grow, w.steps);
+  w.cells += (unsigned long long)m * (end + 1);
+  w.passes++;
+  const int start = end - uni(r.lastcol);
+  tb = tbx + start;
+  te = tbx + end + 1;
+  edit_dist = best;
+  align_len = (m + (te - tb) + best) / 2;
+  return true;
+}
+
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 8)
+void k_pair(const ReadTable R, const ovl_record *__restrict__ in, const uint32_t *__restrict__ order,
+            const uint32_t n_olaps, ovl_record *__restrict__ out, uint32_t *__restrict__ flags_out,
+            unsigned long long *__restrict__ cells_out,
+            unsigned long long *__restrict__ steps_out, uint32_t *__restrict__ passes_out,
+            uint32_t *__restrict__ scratch,
+            const uint64_t scratch_words, const double erate, const uint32_t min_len,
+            const int partial, const int invert) {
+  __shared__ uint32_t s_row[WAVES_PER_BLOCK][LDS_WORDS];
+  const int lane = threadIdx.x & 63;
+  const int wave = uni((int)(threadIdx.x >> 6));
+  const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;   // uniform: see `wave`
+  WaveCtx w;
+  w.lrow = s_row[wave];
+  w.grow = scratch ? scratch + gw * scratch_words : nullptr;
+  w.erate = erate;
+  const uint64_t HM = (1ull << 21) - 1;
+
+  // Overlaps come longest first in `order`; wave g takes slots g, g + waves, ... (the slot
+  // arithmetic is scalar: nothing in this loop depends on the lane)
+  const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
+  for (uint32_t slot = (uint32_t)gw; slot < n_olaps; slot += n_waves) {
+    const uint32_t oi = (uint32_t)uni((int)order[slot]);
+    w.cells = 0;
+    w.steps = 0;
+    w.passes = 0;
+
+    uint32_t a_iid = (uint32_t)uni((int)in[oi].a_iid), b_iid = (uint32_t)uni((int)in[oi].b_iid);
+    const uint64_t d0 = in[oi].dat[0], d1 = in[oi].dat[1];
+    int ahg5 = uni((int)(d0 & HM)), ahg3 = uni((int)((d0 >> 21) & HM));
+    int bhg5 = uni((int)(d1 & HM)), bhg3 = uni((int)((d1 >> 21) & HM));
+    const uint32_t d0_hi = (uint32_t)uni((int)(d0 >> 32));    // evalue 10.., flipped 22, flags
+    const uint32_t d1_hi = (uint32_t)uni((int)(d1 >> 32));
+    const uint32_t d1_lo = (uint32_t)uni((int)d1);
+    const bool flipped = (d0_hi >> 22) & 1;
+    if (invert) {                                             // ovOverlap::swapIDs
+      const uint32_t ti = a_iid; a_iid = b_iid; b_iid = ti;
+      const int o_a5 = ahg5, o_a3 = ahg3, o_b5 = bhg5, o_b3 = bhg3;
+      if (!flipped) { ahg5 = o_b5; ahg3 = o_b3; bhg5 = o_a5; bhg3 = o_a3; }
+      else          { ahg5 = o_b3; ahg3 = o_b5; bhg5 = o_a3; bhg3 = o_a5; }
+    }
+    const uint32_t ra = a_iid - R.first_iid, rb = b_iid - R.first_iid;   // checked on the host
+    const int alen = uni((int)R.len[ra]), blen = uni((int)R.len[rb]);
+    const Oriented A{R.fwd + R.off[ra], alen};
+    const Oriented B{(flipped ? R.rc : R.fwd) + R.off[rb], blen};
+
+    int abgn = ahg5, aend = alen - ahg3, bbgn = bhg5, bend = blen - bhg3;
+    int align_len = 1, edit_dist = INT_MAX;
+    uint32_t fl = 0;
+    // the record's hangs, as the reference keeps them in *ovl, and the working copies of the
+    // dovetail extensions (:487-491)
+    int r_a5 = ahg5, r_a3 = ahg3, r_b5 = bhg5, r_b3 = bhg3;
+    int a5 = 0, a3 = 0, b5 = 0, b3 = 0;
+
+    // recomputeOverlaps as seven steps, so that the aligner is inlined once: the two initial
+    // alignments, the four dovetail extensions in the reference's order, finalAlignment
+    enum { INIT_A, INIT_B, EXT5B, EXT5A, EXT3A, EXT3B, FINAL, N_STEPS };
+    bool live = true;
+    if ((uint32_t)(aend - abgn) < min_len || (uint32_t)(bend - bbgn) < min_len) {
+      fl |= F_SKIPPED;
+      live = false;
+    }
+    for (int step = INIT_A; step < N_STEPS && live; step++) {
+      bool run = true, q_is_b = false;
+      int slop = 100;                           // (a hang already zeroed) * erate + 100
+      switch (step) {
+        case INIT_A: q_is_b = true; slop = MHAP_SLOP; break;
+        case INIT_B: q_is_b = false; slop = MHAP_SLOP; break;
+        case EXT5B:
+          run = a5 >= b5 && b5 > 0;
+          if (run) { a5 -= b5; b5 = 0; q_is_b = true; }
+          break;
+        case EXT5A:
+          run = b5 >= a5 && a5 > 0;
+          if (run) { b5 -= a5; a5 = 0; q_is_b = false; }
+          break;
+        case EXT3A:
+          run = b3 >= a3 && a3 > 0;
+          if (run) { b3 -= a3; a3 = 0; q_is_b = false; }
+          break;
+        case EXT3B:
+          run = a3 >= b3 && b3 > 0;
+          if (run) { a3 -= b3; b3 = 0; q_is_b = true; }
+          break;
+        default: break;
+      }
+      if (step == FINAL) {
+        r_a5 = a5; r_a3 = a3; r_b5 = b5; r_b3 = b3;
+        // finalAlignment (:308-341): global, over the record's spans
+        const int fa = r_a5, fe = alen - r_a3, fb = r_b5, fbe = blen - r_b3;
+        const int m = fe - fa, n = fbe - fb;
+        if (m > 0 && n > 0) {
+          const int k = max_edit(m, n, erate);
+          const Seq q{A.p + fa, m, 0};
+          const Seq t{B.p + fb, n, 0};
+          PassOut g = dp_pass(q, t, 1, INT_MIN, w.lrow, w.grow, w.steps);
+          w.cells += (unsigned long long)m * n;
+          w.passes++;
+          const int ed = uni(g.fin);
+          if (ed <= k) { edit_dist = ed; align_len = (m + n + ed) / 2; }
+        }
+        continue;
+      }
+      if (!run) continue;
+      if (step >= EXT5B) { abgn = a5; aend = alen - a3; bbgn = b5; bend = blen - b3; }
+      bool ok;
+      if (q_is_b) ok = extend_alignment(w, B, bbgn, bend, A, abgn, aend, slop, edit_dist, align_len);
+      else        ok = extend_alignment(w, A, abgn, aend, B, bbgn, bend, slop, edit_dist, align_len);
+      switch (step) {
+        case INIT_A: if (!ok) fl |= F_FAILEXTA; break;
+        case INIT_B:
+          if (!ok) fl |= F_FAILEXTB;
+          if (align_len == 1) {
+            fl |= F_FAILEXT;
+            live = false;
+          } else {
+            r_a5 = abgn; r_a3 = alen - aend; r_b5 = bbgn; r_b3 = blen - bend;
+            if (partial) {
+              fl |= F_PARTIAL;
+              live = false;
+            } else if ((r_a5 == 0 || r_b5 == 0) && (r_a3 == 0 || r_b3 == 0)) {
+              fl |= F_DOVETAIL;
+              live = false;
+            }
+            a5 = r_a5; a3 = r_a3; b5 = r_b5; b3 = r_b3;
+          }
+          break;
+        case EXT5B: if (ok) a5 = abgn; else { a5 = r_a5; b5 = r_b5; } fl |= F_EXT5B; break;
+        case EXT5A: if (ok) b5 = bbgn; else { b5 = r_b5; a5 = r_a5; } fl |= F_EXT5A; break;
+        case EXT3A: if (ok) b3 = blen - bend; else { b3 = r_b3; a3 = r_a3; } fl |= F_EXT3A; break;
+        case EXT3B: if (ok) a3 = alen - aend; else { a3 = r_a3; b3 = r_b3; } fl |= F_EXT3B; break;
+        default: break;
+      }
+    }
+    const double e_rate = edit_dist / (double)align_len;
+    uint32_t evalue = MAX_EVALUE, for_obt = 0, for_dup = 0, for_utg = 0;
+    if ((uint32_t)align_len < min_len || e_rate > erate) {
+      fl |= F_FAILED;
+    } else {
+      fl |= F_PASSED;
+      evalue = e_rate < (MAX_EVALUE / 10000.0) ? (uint32_t)(int)(10000.0 * e_rate + 0.5) : MAX_EVALUE;
+      evalue &= MAX_EVALUE;
+      for_obt = for_dup = partial ? 1 : 0;
+      for_utg = (!partial && (r_a5 == 0 || r_b5 == 0) && (r_a3 == 0 || r_b3 == 0)) ? 1 : 0;
+    }
+    // dat[0]: ahg5:21 ahg3:21 evalue:12 flipped forOBT forDUP forUTG extra1:6
+    const uint64_t o0 = ((uint64_t)r_a5 & HM) | (((uint64_t)r_a3 & HM) << 21) |
+                        ((uint64_t)evalue << 42) | ((uint64_t)(flipped ? 1 : 0) << 54) |
+                        ((uint64_t)for_obt << 55) | ((uint64_t)for_dup << 56) |
+                        ((uint64_t)for_utg << 57) | ((uint64_t)(d0_hi >> 26) << 58);
+    // dat[1]: bhg5:21 bhg3:21 span:21 extra2:1 -- span and extra2 are carried over
+    const uint64_t keep1 = (((uint64_t)d1_hi << 32) | d1_lo) & ~((1ull << 42) - 1);
+    const uint64_t o1 = ((uint64_t)r_b5 & HM) | (((uint64_t)r_b3 & HM) << 21) | keep1;
+    // every lane holds the same values and stores them: no lane-dependent branch in this loop
+    out[oi].a_iid = a_iid;
+    out[oi].b_iid = b_iid;
+    out[oi].dat[0] = o0;
+    out[oi].dat[1] = o1;
+    flags_out[oi] = fl;
+    cells_out[oi] = w.cells;
+    steps_out[oi] = w.steps;
+    passes_out[oi] = w.passes;
+  }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ host
+
+struct pair_ctx {
+  int device = 0;
+  pair_params P{};
+  hipStream_t stream = nullptr;
+  uint32_t first_iid = 0, nreads = 0;
+  std::vector<uint32_t> len;
+  uint32_t max_len = 0;
+  uint8_t *d_fwd = nullptr, *d_rc = nullptr;
+  uint64_t *d_off = nullptr;
+  uint32_t *d_len = nullptr;
+  pair_stats S{};
+};
+
+namespace {
+
+int check_params(const pair_params *p) {
+  if (!p) return fail(PAIR_ERR_BAD_PARAM, "null parameters");
+  if (!(p->max_erate >= 0.0) || p->max_erate > 1.0)
+    return fail(PAIR_ERR_BAD_PARAM, "max_erate %g outside [0, 1]", p->max_erate);
+  if (p->min_overlap_length == 0)
+    return fail(PAIR_ERR_BAD_PARAM, "min_overlap_length 0 is not supported: the reference "
+                                    "aligns empty spans there; use 1 or more");
+  return PAIR_OK;
+}
+
+void free_reads(pair_ctx *c) {
+  if (c->d_fwd) (void)hipFree(c->d_fwd);
+  if (c->d_rc) (void)hipFree(c->d_rc);
+  if (c->d_off) (void)hipFree(c->d_off);
+  if (c->d_len) (void)hipFree(c->d_len);
+  c->d_fwd = c->d_rc = nullptr;
+  c->d_off = nullptr;
+  c->d_len = nullptr;
+  c->nreads = 0;
+  c->len.clear();
+  c->max_len = 0;
+}
+
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+}  // namespace
+
+extern "C" {
+
+void pair_params_init(pair_params *p) {
+  if (!p) return;
+  p->max_erate = 0.12;          // overlapPair.C:680
+  p->min_overlap_length = 1;    // the reference's default 0 is refused
+  p->partial = 0;
+  p->invert = 0;
+}
+
+const char *pair_last_error(void) { return g_err.c_str(); }
+int pair_abi_version(void) { return PAIR_ABI_VERSION; }
+
+int pair_ctx_create(const pair_params *p, int device, pair_ctx **out) {
+  if (!out) return fail(PAIR_ERR_BAD_PARAM, "null out");
+  *out = nullptr;
+  if (int rc = check_params(p)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(PAIR_ERR_NO_DEVICE, "no HIP device %d", device);
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(PAIR_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
+                prop.gcnArchName);
+  HIP_TRY(hipSetDevice(device));
+  pair_ctx *c = new pair_ctx;
+  c->device = device;
+  c->P = *p;
+  hipError_t e = hipStreamCreate(&c->stream);
+  if (e != hipSuccess) {
+    delete c;
+    return fail(PAIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
+  }
+  *out = c;
+  return PAIR_OK;
+}
+
+void pair_ctx_destroy(pair_ctx *c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  free_reads(c);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+
+int pair_set_params(pair_ctx *c, const pair_params *p) {
+  if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
+  if (int rc = check_params(p)) return rc;
+  c->P = *p;
+  return PAIR_OK;
+}
+
+int pair_load_reads_device(pair_ctx *c, uint32_t first_iid, uint32_t nreads,
+                           const uint8_t *d_bases, const uint64_t *d_offsets,
+                           const uint32_t *h_lengths) {
+  if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
+  if (nreads && (!d_bases || !d_offsets || !h_lengths))
+    return fail(PAIR_ERR_BAD_PARAM, "null read buffers");
+  if ((uint64_t)first_iid + nreads > 0xffffffffull)
+    return fail(PAIR_ERR_BAD_PARAM, "read IDs beyond 32 bits");
+  HIP_TRY(hipSetDevice(c->device));
+  free_reads(c);
+  std::vector<uint64_t> off(nreads);
+  uint64_t total = 0;
+  uint32_t mx = 0;
+  for (uint32_t i = 0; i < nreads; i++) {
+    if (h_lengths[i] > (1u << 21) - 1)
+      return fail(PAIR_ERR_BAD_INPUT, "read %u is %u bases, beyond AS_MAX_READLEN", first_iid + i,
+                  h_lengths[i]);
+    off[i] = total;
+    total += h_lengths[i];
+    mx = std::max(mx, h_lengths[i]);
+  }
+  DevBuf<uint32_t> bad;
+  HIP_TRY(bad.alloc(1));
+  HIP_TRY(hipMalloc((void **)&c->d_fwd, std::max<uint64_t>(total, 1)));
+  HIP_TRY(hipMalloc((void **)&c->d_rc, std::max<uint64_t>(total, 1)));
+  HIP_TRY(hipMalloc((void **)&c->d_off, std::max<size_t>(nreads, 1) * 8));
+  HIP_TRY(hipMalloc((void **)&c->d_len, std::max<size_t>(nreads, 1) * 4));
+  HIP_TRY(hipMemsetAsync(bad.p, 0, 4, c->stream));
+  uint32_t h_bad = 0;
+  if (nreads) {
+    HIP_TRY(hipMemcpyAsync(c->d_off, off.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_len, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
+    const uint32_t grid = std::min<uint32_t>(nreads, 4096);
+    hipLaunchKernelGGL(k_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, c->d_off,
+                       c->d_len, nreads, c->d_fwd, c->d_rc, bad.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (h_bad) {
+    free_reads(c);
+    return fail(PAIR_ERR_BAD_INPUT, "a read holds a byte outside ACGTN");
+  }
+  c->first_iid = first_iid;
+  c->nreads = nreads;
+  c->len.assign(h_lengths, h_lengths + nreads);
+  c->max_len = mx;
+  return PAIR_OK;
+}
+
+int pair_load_reads(pair_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
+                    const uint64_t *offsets, const uint32_t *lengths) {
+  if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
+  if (nreads && (!bases || !offsets || !lengths))
+    return fail(PAIR_ERR_BAD_PARAM, "null read buffers");
+  HIP_TRY(hipSetDevice(c->device));
+  uint64_t bytes = 0;
+  for (uint32_t i = 0; i < nreads; i++) bytes = std::max(bytes, offsets[i] + lengths[i]);
+  DevBuf<uint8_t> d_b;
+  DevBuf<uint64_t> d_o;
+  HIP_TRY(d_b.alloc(bytes));
+  HIP_TRY(d_o.alloc(nreads));
+  if (bytes) HIP_TRY(hipMemcpy(d_b.p, bases, bytes, hipMemcpyHostToDevice));
+  if (nreads) HIP_TRY(hipMemcpy(d_o.p, offsets, nreads * 8ull, hipMemcpyHostToDevice));
+  return pair_load_reads_device(c, first_iid, nreads, d_b.p, d_o.p, lengths);
+}
+
+int pair_realign(pair_ctx *c, const ovl_record *in, uint64_t n, ovl_record *out) {
+  if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
+  if (n && (!in || !out)) return fail(PAIR_ERR_BAD_PARAM, "null records");
+  if (n > 0xfffffff0ull) return fail(PAIR_ERR_BAD_PARAM, "more than 2^32 overlaps in one call");
+  c->S = pair_stats{};
+  if (n == 0) return PAIR_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const uint64_t HM = (1ull << 21) - 1;
+  // the checks the reference leaves out, and the cost estimate the order comes from
+  std::vector<uint64_t> est(n);
+  bool need_scratch = false;
+  for (uint64_t i = 0; i < n; i++) {
+    uint32_t a = in[i].a_iid, b = in[i].b_iid;
+    uint64_t a5 = in[i].dat[0] & HM, a3 = (in[i].dat[0] >> 21) & HM;
+    uint64_t b5 = in[i].dat[1] & HM, b3 = (in[i].dat[1] >> 21) & HM;
+    if (c->P.invert) { std::swap(a, b); std::swap(a5, b5); std::swap(a3, b3); }
+    if (a < c->first_iid || a - c->first_iid >= c->nreads || b < c->first_iid ||
+        b - c->first_iid >= c->nreads)
+      return fail(PAIR_ERR_BAD_INPUT, "overlap %llu names read %u or %u, not loaded",
+                  (unsigned long long)i, a, b);
+    const uint64_t al = c->len[a - c->first_iid], bl = c->len[b - c->first_iid];
+    if (a5 + a3 > al || b5 + b3 > bl)
+      return fail(PAIR_ERR_BAD_INPUT, "overlap %llu: hangs beyond its reads (%u: %llu+%llu of "
+                  "%llu, %u: %llu+%llu of %llu)", (unsigned long long)i, a,
+                  (unsigned long long)a5, (unsigned long long)a3, (unsigned long long)al, b,
+                  (unsigned long long)b5, (unsigned long long)b3, (unsigned long long)bl);
+    const uint64_t as = al - a5 - a3, bs = bl - b5 - b3;
+    est[i] = bs * std::min<uint64_t>(al, as + 2 * MHAP_SLOP);
+    // a dovetail extension can stretch a span to its whole read, so the reads decide
+    if (std::max(al, bl) > PAIR_LDS_COLUMNS) need_scratch = true;
+  }
+  std::vector<uint32_t> order(n);
+  std::iota(order.begin(), order.end(), 0u);
+  std::stable_sort(order.begin(), order.end(),
+                   [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
+
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+  const uint64_t max_blocks = (uint64_t)prop.multiProcessorCount * 8;   // 8 waves per SIMD
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
+                                                       max_blocks);
+  const uint64_t scratch_words = need_scratch ? ((uint64_t)c->max_len + 15) / 16 : 0;
+
+  DevBuf<ovl_record> d_in, d_out;
+  DevBuf<uint32_t> d_order, d_flags, d_passes, d_scratch;
+  DevBuf<unsigned long long> d_cells, d_steps;
+  HIP_TRY(d_in.alloc(n));
+  HIP_TRY(d_out.alloc(n));
+  HIP_TRY(d_order.alloc(n));
+  HIP_TRY(d_flags.alloc(n));
+  HIP_TRY(d_passes.alloc(n));
+  HIP_TRY(d_cells.alloc(n));
+  HIP_TRY(d_steps.alloc(n));
+  if (scratch_words) HIP_TRY(d_scratch.alloc(scratch_words * blocks * WAVES_PER_BLOCK));
+  HIP_TRY(hipMemcpyAsync(d_in.p, in, n * sizeof(ovl_record), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(d_flags.p, 0, n * 4, c->stream));
+
+  ReadTable R{c->d_fwd, c->d_rc, c->d_off, c->d_len, c->first_iid, c->nreads};
+  hipEvent_t e0, e1;
+  HIP_TRY(hipEventCreate(&e0));
+  HIP_TRY(hipEventCreate(&e1));
+  HIP_TRY(hipEventRecord(e0, c->stream));
+  hipLaunchKernelGGL(k_pair, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, c->stream, R, d_in.p,
+                     d_order.p, (uint32_t)n, d_out.p, d_flags.p, d_cells.p, d_steps.p, d_passes.p,
+                     d_scratch.p, scratch_words, c->P.max_erate, c->P.min_overlap_length,
+                     c->P.partial ? 1 : 0, c->P.invert ? 1 : 0);
+  hipError_t le = hipGetLastError();
+  HIP_TRY(hipEventRecord(e1, c->stream));
+  std::vector<ovl_record> h_out(n);
+  std::vector<uint32_t> fl(n), ps(n);
+  std::vector<unsigned long long> cells(n), steps(n);
+  hipError_t se = hipStreamSynchronize(c->stream);
+  float ms = 0;
+  if (le == hipSuccess && se == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  HIP_TRY(le);
+  HIP_TRY(se);
+  HIP_TRY(hipMemcpy(h_out.data(), d_out.p, n * sizeof(ovl_record), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(fl.data(), d_flags.p, n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ps.data(), d_passes.p, n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cells.data(), d_cells.p, n * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(steps.data(), d_steps.p, n * 8, hipMemcpyDeviceToHost));
+  memcpy(out, h_out.data(), n * sizeof(ovl_record));
+  pair_stats &S = c->S;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t f = fl[i];
+    if (!(f & (F_PASSED | F_FAILED)))
+      return fail(PAIR_ERR_HIP, "overlap %llu was not processed", (unsigned long long)i);
+    S.n_skipped += !!(f & F_SKIPPED);
+    S.n_passed += !!(f & F_PASSED);
+    S.n_failed += !!(f & F_FAILED);
+    S.n_fail_ext_a += !!(f & F_FAILEXTA);
+    S.n_fail_ext_b += !!(f & F_FAILEXTB);
+    S.n_fail_ext += !!(f & F_FAILEXT);
+    S.n_partial += !!(f & F_PARTIAL);
+    S.n_dovetail += !!(f & F_DOVETAIL);
+    S.n_ext5a += !!(f & F_EXT5A);
+    S.n_ext3a += !!(f & F_EXT3A);
+    S.n_ext5b += !!(f & F_EXT5B);
+    S.n_ext3b += !!(f & F_EXT3B);
+    S.dp_cells += cells[i];
+    S.dp_steps += steps[i];
+    S.dp_passes += ps[i];
+  }
+  S.scratch_bytes = scratch_words * 4 * blocks * WAVES_PER_BLOCK;
+  S.ms_kernel = ms;
+  return PAIR_OK;
+}
+
+int pair_get_stats(const pair_ctx *c, pair_stats *out) {
+  if (!c || !out) return fail(PAIR_ERR_BAD_PARAM, "null argument");
+  *out = c->S;
+  return PAIR_OK;
+}
+
+}  // extern "C"

@@ -404,3 +404,44 @@ def format_line(r, hash_base: int = 1, num_hash: int = 0, query_base: int = 1) -
     return (f"{w0} {w1} {java_fixed6(r['erate'])} {java_fixed6(r['raw'])} 0 "
             f"{int(r['a_bgn'])} {int(r['a_end'])} {int(r['a_len'])} {int(r['o'])} "
             f"{int(r['b_bgn'])} {int(r['b_end'])} {int(r['b_len'])}")
+
+
+def to_overlaps(records, rs, hash_base: int = 1, num_hash: int = 0, query_base: int = 1
+                ) -> np.ndarray:
+    """MHAP result records as the ovOverlap records mhapConvert writes for their text lines
+    (src/mhap/mhapConvert.C:116-170), so that they go on to `OverlapPair.realign` or
+    `write_ovb` with no file in between.  The IDs take the route of the text (format_line's
+    words, then a_iid = word + baseIDquery - numIDhash, b_iid = word + baseIDhash, in 32
+    bits); a line whose two IDs agree is left out; a flipped B swaps its hangs; the error rate
+    is the line's %.6f text read back, encoded as ovOverlap::erate does; forOBT / forDUP /
+    forUTG are set.  Hangs beyond a read's stored length raise, where the reference prints
+    INVALID OVERLAP and stops."""
+    from .overlap_in_core import RECORD_DTYPE
+    M32, HM = 0xFFFFFFFF, (1 << 21) - 1
+    lens = rs.lengths
+    out = []
+    for r in records:
+        w0 = (int(r["a"]) - (query_base - 1) + num_hash) & M32
+        w1 = (int(r["b"]) - (hash_base - 1)) & M32
+        a = (w0 + (query_base - 1) - num_hash) & M32
+        b = (w1 + (hash_base - 1)) & M32
+        if a == b:
+            continue
+        ahg5 = int(r["a_bgn"]) & HM
+        ahg3 = (int(r["a_len"]) - int(r["a_end"])) & HM
+        flipped = int(r["o"]) != 0
+        if not flipped:
+            bhg5, bhg3 = int(r["b_bgn"]) & HM, (int(r["b_len"]) - int(r["b_end"])) & HM
+        else:
+            bhg3, bhg5 = int(r["b_bgn"]) & HM, (int(r["b_len"]) - int(r["b_end"])) & HM
+        e = float(java_fixed6(r["erate"]))
+        evalue = int(10000.0 * e + 0.5) if e < 4095 / 10000.0 else 4095
+        alen = int(lens[a - rs.first_iid])
+        blen = int(lens[b - rs.first_iid])
+        if alen < ahg5 + ahg3 or blen < bhg5 + bhg3:
+            raise ValueError(f"INVALID OVERLAP {a} (len {alen}) {b} (len {blen}) hangs "
+                             f"{ahg5} {ahg3} - {bhg5} {bhg3} flip {int(flipped)}")
+        d0 = ahg5 | (ahg3 << 21) | ((evalue & 0xfff) << 42) | (int(flipped) << 54) | (7 << 55)
+        d1 = bhg5 | (bhg3 << 21)
+        out.append((a, b, d0, d1))
+    return np.array(out, dtype=RECORD_DTYPE)
