@@ -198,6 +198,49 @@ def build_pair_cli(force: bool = False, verbose: bool = True) -> str:
     return PAIR_CLI_OUT
 
 
+FE_OUT = os.path.join(OUT_DIR, "libcanu_fe.so")
+FE_DEPS = [os.path.join(CSRC, "fe.hip"), os.path.join(HERE, "..", "include", "canu_fe.h"),
+           os.path.join(HERE, "..", "include", "canu_ovl.h")]
+
+
+def build_fe(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_fe.so: findErrors, read error detection from the overlaps."""
+    if not force and not _stale(FE_OUT, FE_DEPS):
+        return FE_OUT
+    os.makedirs(OUT_DIR, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, *HIPCC_FLAGS, "-o", FE_OUT + ".tmp", os.path.join(CSRC, "fe.hip")]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(FE_OUT + ".tmp", FE_OUT)
+    return FE_OUT
+
+
+FE_CLI_OUT = os.path.join(BIN_DIR, "findErrors")
+
+
+def build_fe_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/findErrors: the command line canu's red.sh runs (host C++ over
+    libcanu_fe.so, found next to it through the rpath)."""
+    lib = build_fe(verbose=verbose)
+    src = os.path.join(CSRC, "fe_main.cpp")
+    deps = [src, lib, os.path.join(CSRC, "gkp_store.h"), os.path.join(CSRC, "ovs_reader.h"),
+            *FE_DEPS[1:]]
+    if not force and not _stale(FE_CLI_OUT, deps):
+        return FE_CLI_OUT
+    os.makedirs(BIN_DIR, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
+           "-o", FE_CLI_OUT + ".tmp", src, "-L" + OUT_DIR, "-lcanu_fe",
+           "-Wl,-rpath,$ORIGIN/../lib", "-Wl,--allow-shlib-undefined"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(FE_CLI_OUT + ".tmp", FE_CLI_OUT)
+    return FE_CLI_OUT
+
+
 def build(force: bool = False, verbose: bool = True, profile: bool = False) -> str:
     """profile=True builds the instrumented variant (in-kernel cycle stamps, OVL_DEBUG=1
     prints them) as libcanu_ovl_prof.so; load it with CANU_OVL_LIB."""
@@ -225,3 +268,5 @@ if __name__ == "__main__":
         build_emt_cli(force="--force" in sys.argv)
         build_pair(force="--force" in sys.argv)
         build_pair_cli(force="--force" in sys.argv)
+        build_fe(force="--force" in sys.argv)
+        build_fe_cli(force="--force" in sys.argv)
