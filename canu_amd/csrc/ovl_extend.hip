@@ -80,6 +80,8 @@ struct PedOut {
   int32_t mte;
   int32_t nd;              // deltas produced
   int32_t ovf;             // register window overflow: the pair goes to the generic kernel
+  // wave_ped_reg only: where its caller starts the traceback (row, diagonal, Row there)
+  int32_t tb_e, tb_d, tb_last;
 };
 
 // Orders this wave's global-memory accesses across lanes (lane 0 writes, others read, or
@@ -456,9 +458,11 @@ static_assert(64 * OVL_RJ <= OVL_LOGW, "the row log's stripe holds the register 
 #ifdef OVL_PROFILE
 #define PROF_T(v) unsigned long long v = __builtin_amdgcn_s_memtime()
 #define PROF_ADD(acc, a, b) acc += (b) - (a)
+#define PROF_ARG(a) a,
 #else
 #define PROF_T(v)
 #define PROF_ADD(acc, a, b)
+#define PROF_ARG(a)
 #endif
 
 // Staged strands are kept in LDS as BIT PLANES: word w holds bases 32w..32w+31 as
@@ -543,116 +547,9 @@ __device__ __forceinline__ int32_t dpp_upper_across(int32_t v, int32_t next) {
   return __builtin_amdgcn_update_dpp(u, v, 0x130, 0xf, 0xf, false);
 }
 
-// Set_Right_Delta / Set_Left_Delta over the code log of wave_ped_reg: cell (k, d) holds
-// (r << 2 | code), r = max(1 + L[k-1][d], L[k-1][d-1], 1 + L[k-1][d+1]) and code = which
-// one won (0: d, 1: d-1, 2: d+1) with the reference's tie order.  16 rows at a time are
-// loaded into registers (lane = diagonal offset -16..16 from the walk's position), and the
-// walk is scalar: one readlane per row.
 typedef __attribute__((address_space(1))) const int32_t g_ci32;
 typedef __attribute__((address_space(1))) const uint16_t g_cu16;
 typedef __attribute__((address_space(1))) const uint64_t g_cu64;
-
-// Set_Right_Delta / Set_Left_Delta (forward.C:48, reverse.C:52) over the row log of
-// wave_ped_reg: row k's stripe holds L[k][d] (-2 outside the pruned band).  For 16 rows at a
-// time the previous rows are loaded into registers (lane = diagonal offset -31..31 from the
-// window's first position), every lane's step is decided in parallel, and the walk is
-// scalar, one readlane per row.
-//
-// The walk itself is cheap; what it waits for is the log.  So the rows of OVL_TB_G windows
-// are loaded in one burst (one memory round trip instead of one per window), every window of
-// the burst centred at the burst's first position dc.  A window can be walked from these
-// lanes while its first position d stays within 15 of dc: its 16 steps then read lanes
-// 31 + (d - dc) +- 15, inside the lanes 1..61 whose DPP neighbours are real cells.  The
-// first window of a burst always can; when a later one cannot (the path drifted), the next
-// burst starts there.  Measured (10k x 10 kb, records identical): 2 windows per burst the
-// same as 1, 3 windows +3-4 % (the 48 row registers) -- the other waves of the SIMD already
-// hide the log's latency, so the default stays one window per load.
-#ifndef OVL_TB_G
-#define OVL_TB_G 1
-#endif
-template <bool L16, int LW = OVL_LOGW>
-__device__ __forceinline__ void ped_traceback_codes(int32_t *log, int32_t tb_e, int32_t tb_d,
-                                                    int32_t last, int32_t *dst, uint32_t lane,
-                                                    int32_t &last_out, int32_t &nd_out) {
-  constexpr int W = LW;                        // cells per logged row, cell = d mod W
-  // rows per window (lanes cover dc-31..dc+31): 16 keeps the unrolled walk and its code
-  // registers within wave_ped_reg's 80 VGPRs (24 spills; 16 vs 24: -1 % extension time)
-  constexpr int TBR = 16;
-  constexpr int G = OVL_TB_G;                  // windows per burst of log loads
-  g_ci32 *rows = (g_ci32 *)log;
-  typedef __attribute__((address_space(1))) const int16_t g_ci16;
-  g_ci16 *rows16 = (g_ci16 *)log;
-  typedef __attribute__((address_space(1))) int32_t g_i32;
-  g_i32 *gdst = (g_i32 *)dst;                  // global, not flat (see wave_ped_reg's log)
-  vm_sync();                                  // the log is complete
-  int32_t d = __builtin_amdgcn_readfirstlane(tb_d);
-  last = __builtin_amdgcn_readfirstlane(last);
-  int32_t kh = __builtin_amdgcn_readfirstlane(tb_e);
-  int32_t nd = 0;
-  while (kh >= 1) {
-    const int32_t dc = d;
-    const int32_t cell = (dc - 31 + (int32_t)(lane < 63 ? lane : 62)) & (W - 1);
-    int32_t V[G * TBR];
-#pragma unroll
-    for (int i = 0; i < G * TBR; i++) {
-#ifdef OVL_ATTR_TB_FIXED                       // traffic attribution only (wrong results)
-      const int32_t kk = 0;
-#else
-      const int32_t kk = kh - 1 - i < 0 ? 0 : kh - 1 - i;   // row k-1 for k = kh - i
-#endif
-      if constexpr (L16) V[i] = (int32_t)rows16[(size_t)kk * W + cell];
-      else               V[i] = rows[(size_t)kk * W + cell];
-    }
-#pragma unroll 1
-    for (int g = 0; g < G; g++) {
-      if (g > 0) {
-        const int32_t off = d - dc;
-        if (kh < 1 || off > 15 || off < -15) break;
-      }
-      // Every lane's winner first, lane-parallel (VALU, DPP neighbours): C[i] at lane x is
-      // (the value the walk would take as `last`) << 2 | (from + 1), with the reference's
-      // order -- d-1 only if strictly better than d, d+1 only if strictly better than both.
-      // The walk is then one readlane and a few scalar operations per row; the window's
-      // deltas collect in one VGPR (lane j = its j-th delta) stored once per window.
-      const int32_t nsteps = kh < TBR ? kh : TBR;
-      int32_t C[TBR];
-#pragma unroll
-      for (int i = 0; i < TBR; i++) {
-        const int32_t v = V[i];
-        const int32_t vm = dpp_from_lower(v, -2), vp = dpp_from_upper(v, -2);
-        const int32_t a = v + 1, c = vp + 1;
-        const int32_t m = vm > a ? vm : a;
-        const int32_t f = c > m ? 2 : (vm > a ? 0 : 1);
-        C[i] = ((f == 0 ? vm : vp) << 2) | f;
-      }
-      // the next window's rows move down (register moves; with G == 1 there are none)
-#pragma unroll
-      for (int i = 0; i + TBR < G * TBR; i++) V[i] = V[i + TBR];
-      __builtin_amdgcn_sched_barrier(0);
-      int32_t buf = 0, nb = 0;
-      int32_t x = 31 + d - dc;                 // lane of diagonal d
-#pragma unroll
-      for (int i = 0; i < TBR; i++) {
-        if (i < nsteps) {
-          const int32_t w = __builtin_amdgcn_readlane(C[i], x);
-          const int32_t f3 = w & 3, nl = w >> 2;   // f3: 0 d-1, 1 d, 2 d+1
-          const int32_t val = f3 == 0 ? nl - last - 1 : last - nl;
-          buf = (int32_t)lane == nb ? val : buf;
-          const int32_t mv = f3 != 1;
-          nb += mv;
-          last = mv ? nl : last;
-          x += f3 - 1;
-        }
-      }
-      d = dc + x - 31;
-      if ((int32_t)lane < nb) gdst[nd + (int32_t)lane] = buf;
-      nd += nb;
-      kh -= TBR;
-    }
-  }
-  last_out = last;
-  nd_out = nd;
-}
 
 // Scalar copies of wave-uniform values: arguments of a non-inlined function arrive in
 // VGPRs, so without these a loop bound or branch on them is compiled as divergent
@@ -670,6 +567,157 @@ __device__ __forceinline__ double uni(double v) {
   const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)b);
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)(b >> 32));
   return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+
+// Set_Right_Delta / Set_Left_Delta (forward.C:48, reverse.C:52) over the row log of
+// wave_ped_reg: row k's stripe holds L[k][d] (-2 outside the pruned band).  OVL_TBR rows at a
+// time are loaded into registers (lane 31 + o = diagonal offset o from the window's first
+// position), every lane's step is decided in parallel, and the walk is scalar, one readlane
+// per row.
+//
+// The traceback is a function of its own (not inlined into wave_ped_reg): its window
+// registers are then allocated apart from the row loop's, which is what bounded the window
+// at 16 rows while it was inlined.  The walk's i-th step (i = 0 .. R-1) is taken at a lane
+// within i of lane 31, and a lane's winner reads its two neighbours, so a window of R rows
+// reads lanes 31-R .. 31+R: R <= 30 keeps them inside the 63 lanes whose DPP neighbours are
+// real cells.
+//
+// Winners: with the reference's order (stay on d; d-1 only if strictly better; d+1 only if
+// strictly better than both) the winner and the value the walk takes as `last` are one
+// signed maximum of three keys, ((v + 1) << 3) | 4 for d, (vm << 3) | 3 for d-1 and
+// ((vp + 1) << 3) | 1 for d+1 (the -2 sentinel keeps its order under the signed shift).
+// With u = (v << 3) + 12 the keys are u, u[d-1] - 9 and u[d+1] - 3: one shift-add, two DPP
+// adds and a v_max3 per row, no compare -> select pair.  The low two bits of a key, read as a
+// signed number, are the walk's step (0, -1, +1); `last` is key >> 3 for d-1 and
+// (key >> 3) - 1 for d+1.
+//
+// One window per load: 2 windows per burst measured the same and 3 slower (round 5) -- the
+// other waves of the SIMD already hide the log's latency.  Loading only the lanes a window's
+// rows can reach (in groups of 8 rows, the other lanes keeping the sentinel) measured
+// 0.4 % slower than loading every lane, and windows of 16, 20, 24 and 30 rows measured within
+// 0.4 % of each other (profiles/r08a_ab.txt): 24 rows, 40 VGPRs, nothing saved or spilled.
+#ifndef OVL_TBR
+#define OVL_TBR 24               // rows per traceback window (<= 30)
+#endif
+static_assert(OVL_TBR >= 1 && OVL_TBR <= 30, "the window's walk stays inside lanes 1..61");
+struct TbOut {
+  int32_t last, nd;
+};
+// The scalar walk over a window's winner keys C, rows I .. N-1 (nested, so a short window
+// leaves at its last row): the key at the walk's lane goes to lane I of buf (v_writelane with
+// a constant lane) and its low two bits, read as a signed number, move the walk.  Everything
+// else about the step is decoded from buf afterwards, lane-parallel.
+template <int I, int N>
+__device__ __forceinline__ void tb_walk(const int32_t (&C)[N], int32_t nsteps, int32_t &buf,
+                                        int32_t &x) {
+  if constexpr (I < N) {
+    if (I < nsteps) {
+      const int32_t w = __builtin_amdgcn_readlane(C[I], x);
+      asm("v_writelane_b32 %0, %1, %2" : "+v"(buf) : "s"(w), "n"(I));
+      x += (w << 30) >> 30;
+      tb_walk<I + 1, N>(C, nsteps, buf, x);
+    }
+  }
+}
+template <bool L16, int LW>
+__device__ __attribute__((noinline)) TbOut ped_traceback_win(
+#ifdef OVL_PROFILE
+    unsigned long long *dbg,
+#endif
+    int32_t *log, int32_t tb_e, int32_t tb_d, int32_t last, int32_t *dst, uint32_t lane) {
+  constexpr int W = LW;                        // cells per logged row, cell = d mod W
+  constexpr int TBR = OVL_TBR;
+  typedef typename std::conditional<L16, int16_t, int32_t>::type cell_t;
+  typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+  typedef __attribute__((address_space(1))) const cell_t g_ccell;
+  typedef __attribute__((address_space(1))) int32_t g_i32;
+  PROF_T(pt_tb0);
+  g_cu8 *rows = uni_ptr((g_cu8 *)log);
+  g_i32 *gdst = uni_ptr((g_i32 *)dst);         // global, not flat (see wave_ped_reg's log)
+  vm_sync();                                  // the log is complete
+  int32_t d = uni(tb_d);
+  last = uni(last);
+  int32_t kh = uni(tb_e);
+  int32_t nd = 0;
+  // the keys' two constants, in registers the compiler cannot see through: a DPP add takes
+  // its second operand from a VGPR, and with a literal there the shift stays a move of its own
+  int32_t c9 = -9, c3 = -3;
+  asm volatile("" : "+v"(c9), "+v"(c3));
+  while (kh >= 1) {
+    const int32_t dc = d;
+    const uint32_t cell = (uint32_t)((dc - 31 + (int32_t)lane) & (W - 1)) * (uint32_t)sizeof(cell_t);
+    const int32_t nsteps = kh < TBR ? kh : TBR;
+    int32_t V[TBR];
+#pragma unroll
+    for (int i = 0; i < TBR; i++) {
+#ifdef OVL_ATTR_TB_FIXED                       // traffic attribution only (wrong results)
+      const int32_t kk = 0;
+#else
+      const int32_t kr = kh - 1 - i;           // row k-1 for k = kh - i (row 0 past the end)
+      const int32_t kk = kr & ~(kr >> 31);
+#endif
+      // a scalar row base (kept apart from the lane's offset, so the load takes it as its
+      // scalar address) and one 32-bit lane offset for the whole window
+      g_cu8 *rk = rows + (uint32_t)kk * (uint32_t)(W * sizeof(cell_t));
+      asm("" : "+s"(rk));
+      V[i] = (int32_t)*(g_ccell *)(rk + cell);
+    }
+    // Every lane's winner key first, lane-parallel, in place of the loaded row; the walk
+    // is then one readlane and a few scalar operations per row.
+    // (lanes 0 and 63 have no neighbour on one side: whatever the shift leaves there only
+    // reaches the keys of lanes 0 and 63, which the walk never reads)
+#pragma unroll
+    for (int i = 0; i < TBR; i++) {
+      const int32_t u = (int32_t)(((uint32_t)V[i] << 3) + 12u);
+      const int32_t km = __builtin_amdgcn_update_dpp(0, u, 0x138, 0xf, 0xf, true) + c9;
+      const int32_t kp = __builtin_amdgcn_update_dpp(0, u, 0x130, 0xf, 0xf, true) + c3;
+      const int32_t m = km > u ? km : u;
+      V[i] = kp > m ? kp : m;
+    }
+    // the keys are complete here: without this the compiler sinks each row's adds and max
+    // into the walk and keeps both DPP results of every row live until then
+#pragma unroll
+    for (int i = 0; i < TBR; i++) asm volatile("" : "+v"(V[i]));
+    __builtin_amdgcn_sched_barrier(0);
+    int32_t buf = 0;
+    int32_t x = 31;                            // lane of diagonal d
+    tb_walk<0, TBR>(V, nsteps, buf, x);
+    d = dc + x - 31;
+    // Lane i now holds row i's key.  The rows that left their diagonal are the window's
+    // deltas: their new `last` (and which way they went) is compacted to lanes 0 .. nb-1
+    // (a push through the LDS crossbar, no LDS memory), where a delta's predecessor -- the
+    // `last` it is measured from -- is simply the lane below (lane 0: the incoming `last`).
+    const int32_t f = buf & 7;                 // 4 stay, 3 d-1, 1 d+1
+    const int32_t nlf = (((buf >> 3) - (f == 1 ? 1 : 0)) << 1) | (f == 3 ? 1 : 0);
+    const uint64_t moved = __builtin_amdgcn_ballot_w64((int32_t)lane < nsteps && f != 4);
+    const int32_t nb = (int32_t)__builtin_popcountll(moved);   // <= TBR: bits 0 .. 29 only
+    if (nb) {
+      // the other lanes push to lane 63, which no delta uses
+      const uint32_t rank = __builtin_amdgcn_mbcnt_lo((uint32_t)moved, 0u);
+      const uint32_t to = ((uint32_t)moved >> (lane & 31u)) & (lane < 32u ? 1u : 0u) ? rank : 63u;
+      const int32_t c = __builtin_amdgcn_ds_permute((int32_t)(to << 2), nlf);
+      const int32_t cnl = c >> 1;
+      const int32_t prev = dpp_from_lower(cnl, last);
+      const int32_t val = (c & 1) ? cnl - prev - 1 : prev - cnl;
+      if ((int32_t)lane < nb) gdst[nd + (int32_t)lane] = val;
+      last = __builtin_amdgcn_readlane(cnl, nb - 1);
+      nd += nb;
+    }
+    kh -= TBR;
+  }
+  TbOut o;
+  o.last = last;
+  o.nd = nd;
+#ifdef OVL_PROFILE
+  PROF_T(pt_tb1);
+  if (dbg && lane == 0) {
+    atomicAdd(&dbg[7], pt_tb1 - pt_tb0);
+    atomicAdd(&dbg[11], pt_tb1 - pt_tb0);        // row loop + traceback, as when it was inlined
+    atomicAdd(&dbg[12], pt_tb1 - pt_tb0);        // ... and the extension's time in its calls
+  }
+#endif
+  return o;
 }
 
 // A record loaded with a wave-uniform index, every field as a scalar.
@@ -711,8 +759,7 @@ template <int DIR, typename SS, bool L16, int RJ = OVL_RJ>
 __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
     const ExtendArgs &X, int32_t e_cap, int32_t partial_i, int32_t mbed, double bmv_in,
     double mbts, const lds_u64 *aw, int32_t a0, int32_t m, const lds_u64 *tw, int32_t t0,
-    int32_t n, int32_t limit, int32_t *rows, ml_t *mlim, int32_t *dst,
-    uint32_t lane) {
+    int32_t n, int32_t limit, int32_t *rows, ml_t *mlim, uint32_t lane) {
   SS A, T;
   A.w = aw; A.len = 0;
   T.w = tw; T.len = 0;
@@ -732,6 +779,7 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
   out.leftover = 0;
   out.nd = 0;
   out.ovf = 0;
+  out.tb_e = 0; out.tb_d = 0; out.tb_last = 0;
   if (limit > uni(e_cap) - 2) {                // not this kernel's class: defer the pair
     out.ovf = 1;
     return out;
@@ -1095,13 +1143,12 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
     tb_e = max_score_best_e; tb_d = max_score_best_d;
   }
   if (!finished || out.mte == 0) tb_last = (tb_e == 0) ? row0 : max_score_len;
-  int32_t last = 0, nd = 0;
-  PROF_T(pt_tb0);
-  ped_traceback_codes<L16, LW>(rows, tb_e, tb_d, tb_last, dst, lane, last, nd);
-  out.leftover = last;
-  out.nd = nd;
+  // the traceback is the caller's next call (ped_traceback_win): nd >= 0 asks for it
+  out.tb_e = tb_e;
+  out.tb_d = tb_d;
+  out.tb_last = tb_last;
 #ifdef OVL_PROFILE
-  PROF_T(pt_tb1);
+  PROF_T(pt_end);
   if (X.dbg && lane == 0) {
     atomicAdd(&X.dbg[0], 1ull);
     atomicAdd(&X.dbg[1], pc_rows);
@@ -1109,9 +1156,8 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
     atomicAdd(&X.dbg[3], pc_slide);
     atomicAdd(&X.dbg[4], (unsigned long long)(tb_e > 0 ? tb_e : 0));
     atomicAdd(&X.dbg[6], pc_chunks);
-    atomicAdd(&X.dbg[7], pt_tb1 - pt_tb0);
     atomicAdd(&X.dbg[10], pc_rest);
-    atomicAdd(&X.dbg[11], pt_tb1 - pt_begin);
+    atomicAdd(&X.dbg[11], pt_end - pt_begin);    // ped_traceback_win adds its own cycles
     atomicAdd(&X.dbg[16], pc_a);
     atomicAdd(&X.dbg[17], pc_b);
     atomicAdd(&X.dbg[18], pc_cont);
@@ -1187,6 +1233,8 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
   // A/B, records identical).  Since round 7 the wave index, the pair's and unit's records and
   // the strands are scalar from k_extend on (scratch loads / stores of the staged kernel's
   // body 158 / 85 -> 27 / 17, profiles/r07a_isa.txt)
+  // cells per logged row, as wave_ped_reg<.., RJ> lays the log out
+  constexpr int TB_LW = 64 * RJ > OVL_LOGW ? 64 * RJ : OVL_LOGW;
   Node M;
   M.Start = UNI(Mv.Start); M.Offset = UNI(Mv.Offset); M.Len = UNI(Mv.Len); M.Next = Mv.Next;
   S_Len = UNI(S_Len);
@@ -1219,8 +1267,7 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
     if constexpr (FAST) {
       po = wave_ped_reg<1, SS, L16, RJ>(X, X.e_cap, X.partial, X.min_branch_end_dist,
                                         X.branch_match_value, X.min_branch_tail_slope, A.w, a0,
-                                        am, B.w, b0, bn, error_limit, WM.rows, WM.rmlim, stk,
-                                        lane);
+                                        am, B.w, b0, bn, error_limit, WM.rows, WM.rmlim, lane);
     }
     else
       po = wave_ped<1, SS, L16>(X, A, a0, am, B, b0, bn, error_limit, WM, stk, lane);
@@ -1231,6 +1278,13 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
     if (po.ovf) { r.kind = -1; return r; }
     po.err = UNI(po.err); po.mte = UNI(po.mte); po.a_len = UNI(po.a_len);
     po.t_len = UNI(po.t_len); po.nd = UNI(po.nd); po.leftover = UNI(po.leftover);
+    if constexpr (FAST) {
+      if (po.nd >= 0) {                            // not the exact match: Set_Right_Delta's walk
+        const TbOut tb = ped_traceback_win<L16, TB_LW>(PROF_ARG(X.dbg) WM.rows, po.tb_e, po.tb_d,
+                                                       po.tb_last, stk, lane);
+        po.leftover = UNI(tb.last); po.nd = UNI(tb.nd);
+      }
+    }
     right_errors = po.err;
     rmte = po.mte;
     if (s_first) { S_Hi = po.a_len; T_Hi = po.t_len; }
@@ -1260,8 +1314,7 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
     if constexpr (FAST)
       po = wave_ped_reg<-1, SS, L16, RJ>(X, X.e_cap, X.partial, X.min_branch_end_dist,
                                          X.branch_match_value, X.min_branch_tail_slope, A.w,
-                                         a0, a0 + 1, B.w, b0, b0 + 1, lim, WM.rows, WM.rmlim, LD,
-                                         lane);
+                                         a0, a0 + 1, B.w, b0, b0 + 1, lim, WM.rows, WM.rmlim, lane);
     else
       po = wave_ped<-1, SS, L16>(X, A, a0, a0 + 1, B, b0, b0 + 1, lim, WM, LD, lane);
 #ifdef OVL_PROFILE
@@ -1269,6 +1322,13 @@ __device__ ExtOut extend_alignment(const ExtendArgs &X, const Node &Mv, const SS
     if (X.dbg && lane == 0) atomicAdd(&X.dbg[12], pc3 - pc2);
 #endif
     if (po.ovf) { r.kind = -1; return r; }
+    if constexpr (FAST) {
+      if (UNI(po.nd) >= 0) {                       // Set_Left_Delta's walk
+        const TbOut tb = ped_traceback_win<L16, TB_LW>(PROF_ARG(X.dbg) WM.rows, po.tb_e, po.tb_d,
+                                                       po.tb_last, LD, lane);
+        po.leftover = tb.last; po.nd = tb.nd;
+      }
+    }
     left_errors = po.err;
     lmte = po.mte;
     int32_t a_end = -po.a_len, t_end = -po.t_len;

@@ -102,7 +102,7 @@ EXPORTS = ["ovl_params_init", "ovl_params_finalize", "ovl_ctx_create", "ovl_ctx_
            "ovl_ctx_write_ovb", "ovl_ctx_write_stats", "ovl_set_read_libraries",
            "ovl_hash_limits_init", "ovl_build_hash_batch", "ovl_driver_params_init",
            "ovl_overlap_driver", "ovl_seed_hits", "ovl_probe_ceiling", "ovl_probe_replay",
-           "ovl_export_index", "ovl_import_index"]
+           "ovl_export_index", "ovl_import_index", "ovl_traceback_window_rows"]
 
 _lib = None
 
@@ -162,6 +162,11 @@ def load_library(path: str | None = None):
     lib.ovl_import_index.argtypes = [ctypes.c_void_p, P(_IndexDesc)]
     _lib = lib
     return lib
+
+
+def traceback_window_rows() -> int:
+    """Rows per traceback window of the staged extension kernel (a build constant)."""
+    return int(load_library().ovl_traceback_window_rows())
 
 
 @dataclasses.dataclass

@@ -275,6 +275,11 @@ int         ovl_ctx_write_stats(ovl_ctx *ctx, const char *path);
  * order work around it. */
 void       *ovl_ctx_stream(ovl_ctx *ctx);
 
+/* Rows of the alignment's row log that the staged extension's traceback walks per window
+ * (one global round trip each; OVL_TBR of canu_amd/csrc/ovl_extend.hip).  A build constant,
+ * exported for tests that place alignments around the window edges. */
+int         ovl_traceback_window_rows(void);
+
 /* Measurement only (bench.py's probe roofline; no reference counterpart, ABI 4): the rate
  * of independent random 16-B loads over the CURRENT index table's own allocation
  * (2^tab_bits slots, the table the hash probe looks each query window up in), in G loads/s,
