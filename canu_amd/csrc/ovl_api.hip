@@ -411,6 +411,8 @@ void *ovl_ctx_stream(ovl_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr;
 
 int ovl_traceback_window_rows(void) { return OVL_TBR; }
 
+int ovl_row_end_margin(void) { return OVL_END_MARGIN; }
+
 int ovl_probe_ceiling(ovl_ctx *c, double *gloads_per_s, uint64_t *table_bytes) {
   if (!c || !gloads_per_s || !table_bytes) return fail(OVL_ERR_STATE, "null argument");
   if (!c->have_index || !c->d_tab.p) return fail(OVL_ERR_STATE, "no index table");

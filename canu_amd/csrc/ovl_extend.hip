@@ -601,6 +601,17 @@ __device__ __forceinline__ double uni(double v) {
 #define OVL_TBR 24               // rows per traceback window (<= 30)
 #endif
 static_assert(OVL_TBR >= 1 && OVL_TBR <= 30, "the window's walk stays inside lanes 1..61");
+// Interior rows of wave_ped_reg.  A row's cells start at q <= Longest on diagonals
+// d <= pr + 1, and the first slide step looks at 31 bases.  So on a row with
+//   Longest + OVL_END_MARGIN < m   and   Longest + (pr + 1) + OVL_END_MARGIN < n
+// every in-band cell has min(m - 1 - q, n - 1 - q - d) >= OVL_END_MARGIN > 31 bases left: the
+// first step is never clamped, ends nowhere, and a lane continues exactly when all 31 bases
+// matched.  Such a row skips the per-chunk end bookkeeping (below).  33 is one more than
+// the 32 the argument needs.
+#ifndef OVL_END_MARGIN
+#define OVL_END_MARGIN 33
+#endif
+static_assert(OVL_END_MARGIN >= 32, "an interior row's first slide step must not reach an end");
 struct TbOut {
   int32_t last, nd;
 };
@@ -849,6 +860,11 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
   // one (row 1 needs none: B = -3, pl = pr = 0).
   int32_t end_e = 0;
   int32_t go = limit - 1;                      // the loop runs while go >= 0
+  // The interior test (OVL_END_MARGIN), one signed test of two differences like `go`:
+  // inter >= 0 while both reads' ends are out of the next row's reach.  Row 1 starts from
+  // row0 (Longest is still 0), every later row from values <= Longest.
+  const int32_t m_in = uni(m) - (OVL_END_MARGIN + 1), n_in = uni(n) - (OVL_END_MARGIN + 2);
+  int32_t inter = (m_in - row0) | (n_in - row0);
   while (go >= 0) {
     PROF_T(pt_row);
     const int32_t ML = mlim[e];
@@ -856,11 +872,15 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
     const int32_t jr = (right - B) >> 6;
 
     // ---- A+B per chunk: neighbours from row e-1 (DPP, no LDS), then the first 32-base
-    // slide step of every lane, branch-free (one pass: each unrolled chunk costs a scalar
-    // compare-and-branch on jr) --------------------------------------------------------
-    int32_t NR[J], RM[J];   // row value; lanes: bases left before the end (0 = end)
+    // slide step of every lane, branch-free on an interior row (one pass: each unrolled
+    // chunk costs a scalar compare-and-branch on jr and one on the interior test) --------
+    // The bases a lane has left before an end are not kept: where they are needed (a row
+    // near an end, a continued slide, the end row) they are min(m - NR, n - NR - d) of the
+    // lane's row value; outside the band NR is hugely negative and the count positive.
+    int32_t NR[J];          // row value
     uint64_t need[J];
     uint64_t any = 0;
+    uint64_t endany = 0;    // some lane reached an end
 #pragma unroll
     for (int j = 0; j < J; j++) {
       if (j >= JU && j > jr) break;
@@ -873,11 +893,6 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
       // q = Row - 1 = max(pm - 1, p0, pp): the +1 of the max3 folds into the constants
       const int32_t pm1 = pm - 1;
       const int32_t q = (pm1 > p0 ? pm1 : p0) > pp ? (pm1 > p0 ? pm1 : p0) : pp;
-      // d outside [left, right] sees only -2 sentinels, so Row == -1 there (inside, >= 1):
-      // its limit is hugely negative, so it never slides, ends or survives pruning
-      const int32_t l1 = (m - 1) - q, l2 = (n - 1) - q - d;
-      const int32_t lmin = l1 < l2 ? l1 : l2;
-      const int32_t lim = q >= -1 ? lmin : -(1 << 30);
 
       const int32_t pa = (DIR > 0) ? (a0 + 1) + q : (a0 - 32) - q;
       const int32_t pt = (DIR > 0) ? (t0 + 1) + q + d : (t0 - 32) - q - d;
@@ -896,13 +911,34 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
       // the bit scan), lanes that matched all 31 with more left continue below
       const int32_t run = (DIR > 0) ? (int32_t)__builtin_ctz(mm | 0x80000000u)
                                     : (int32_t)__builtin_clz(mm | 1u);
-      // k = min(run, lim): lim >= 0 (run >= 0), so the row only moves forward
-      const int32_t k = run < lim ? run : lim;
-      NR[j] = q + 1 + k;                       // lim >= 0 inside the band
-      RM[j] = lmin - k;                        // inside: lim - k >= 0; outside: > 0
-      // run == 31 && lim > 31  <=>  min(run, lim - 1) == 31 (run <= 31): one ballot, no
-      // scalar AND of two
-      need[j] = __builtin_amdgcn_ballot_w64((run < lim - 1 ? run : lim - 1) == 31);
+      // An interior row: no first step can reach an end, so a lane moves by its run and
+      // continues when the run is 31.  d outside [left, right] sees only -2 sentinels, so
+      // q == -2 there (inside, >= 0): its row value is set far below every Edit_Match_Limit
+      // (the kept test adds max(d, 0), which can be thousands), and it does not continue.
+      const uint64_t inb = __builtin_amdgcn_ballot_w64(q >= -1);
+      NR[j] = q >= -1 ? q + 1 + run : -(1 << 30);
+      need[j] = __builtin_amdgcn_ballot_w64(run == 31) & inb;
+      // A row within OVL_END_MARGIN of an end replaces both: the step is clamped to the
+      // bases left, and a lane with none left joins the row's end ballot.  This is an `if`
+      // after the interior values, not an if / else around them, and it tests a scalar copy
+      // taken here: so the interior row pays one s_cmp and one untaken branch per chunk.
+      // (As if / else the chunk carried three more scalar instructions, 183.2 against
+      // 181.2 ms on the 10k-read job; on `inter` itself the test's result was shared by the
+      // chunks as a lane mask, two VALU and four scalar instructions per chunk.)
+      if (__builtin_expect(uni(inter) < 0, 0)) {
+        const int32_t l1 = (m - 1) - q, l2 = (n - 1) - q - d;
+        const int32_t lmin = l1 < l2 ? l1 : l2;
+        // outside the band the limit is hugely negative: never slides, ends or survives
+        // pruning
+        const int32_t lim = q >= -1 ? lmin : -(1 << 30);
+        // k = min(run, lim): lim >= 0 (run >= 0), so the row only moves forward
+        const int32_t k = run < lim ? run : lim;
+        NR[j] = q + 1 + k;                       // lim >= 0 inside the band
+        endany |= __builtin_amdgcn_ballot_w64(lmin == k);   // (outside: k = -2^30 < lmin)
+        // run == 31 && lim > 31  <=>  min(run, lim - 1) == 31 (run <= 31): one ballot, no
+        // scalar AND of two
+        need[j] = __builtin_amdgcn_ballot_w64((run < lim - 1 ? run : lim - 1) == 31);
+      }
       any |= need[j];
     }
 #ifdef OVL_PROFILE
@@ -911,46 +947,49 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
     PROF_T(pt_b);
     PROF_ADD(pc_a, pt_row, pt_b);
     // lanes that matched all 31 bases continue (the on-path diagonals): one loop over all
-    // chunks so their LDS loads overlap
+    // chunks so their LDS loads overlap.  They count their own bases left.  On an interior
+    // row they are the only lanes that can reach an end: the row's end ballot is taken here.
     if (any) {
 #pragma unroll
       for (int j = 0; j < J; j++) {
         if (j >= JU && j > jr) break;
         if (need[j]) {
+          // (the ballot stays outside the lanes' branch: taken inside it, the row's exits
+          // were compiled as divergent branches)
+          int32_t left = 1;
           if (need[j] & (1ull << lane)) {
             const int32_t d = B + 64 * j + (int32_t)lane;
-            const int32_t sl = slide_d(NR[j], d, RM[j]);
+            const int32_t l1 = m - NR[j], l2 = n - NR[j] - d;
+            const int32_t rem = l1 < l2 ? l1 : l2;
+            const int32_t sl = slide_d(NR[j], d, rem);
             NR[j] += sl;
-            RM[j] -= sl;
+            left = rem - sl;
           }
+          endany |= __builtin_amdgcn_ballot_w64(left == 0);
 #ifdef OVL_PROFILE
           pc_slide++;
 #endif
         }
       }
     }
-
     PROF_T(pt_cont);
     PROF_ADD(pc_cont, pt_b, pt_cont);
-    // ---- C: end test and Edit_Match_Limit pruning, one pass ---------------------------
+
+    // ---- C: Edit_Match_Limit pruning, one pass ----------------------------------------
     // Only two masks are reduced on the common row: the kept range's left end lies in chunk
     // 0 (the window is anchored at the band's left edge) and its right end in the last
     // chunk, jr.  So chunk 0's and chunk jr's kept masks are kept and the other chunks cost
     // no scalar work; when either is empty (~2 % of rows: the pruning emptied the band's
-    // first or last chunk, or the whole band) every chunk is rescanned below.  The end test
-    // is a per-lane min of the bases left, one ballot per row.  (The per-chunk s_ff1 /
-    // s_flbit / min reduction was 6 scalar instructions per chunk.)
-    int32_t rmin = RM[0];
+    // first or last chunk, or the whole band) every chunk is rescanned below.  (The
+    // per-chunk s_ff1 / s_flbit / min reduction was 6 scalar instructions per chunk.)
     uint64_t km0 = 0, kml = 0;
 #pragma unroll
     for (int j = 0; j < J; j++) {
       if (j >= JU && j > jr) break;
       const int32_t d = B + 64 * j + (int32_t)lane;
-      if (j > 0) rmin = RM[j] < rmin ? RM[j] : rmin;
       kml = __builtin_amdgcn_ballot_w64(NR[j] + (d > 0 ? d : 0) >= ML);
       if (j == 0) km0 = kml;
     }
-    const uint64_t endany = __builtin_amdgcn_ballot_w64(rmin == 0);
     uint32_t nlo, nhi;                         // min window offset of a kept lane; min
                                                // reversed offset (64J-1 - o) of one
     // s_ff1 / s_flbit give ~0u on an empty mask: one signed test of their OR sends the row
@@ -996,7 +1035,9 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
 #pragma unroll
       for (int j = J - 1; j >= 0; j--) {
         if (j >= JU && j > jr) continue;
-        const uint64_t em = __builtin_amdgcn_ballot_w64(RM[j] == 0);
+        const int32_t d = B + 64 * j + (int32_t)lane;
+        const int32_t l1 = m - NR[j], l2 = n - NR[j] - d;
+        const uint64_t em = __builtin_amdgcn_ballot_w64((l1 < l2 ? l1 : l2) == 0);
         if (em) {
           const int32_t l = (int32_t)__builtin_ctzll(em);
           end_d = B + 64 * j + l;
@@ -1057,6 +1098,7 @@ __device__ __attribute__((OVL_PED_ATTR)) PedOut wave_ped_reg(
       }
       pl = nl;
       pr = nr;
+      inter = (m_in - longest) | (n_in - longest - pr);
       PROF_T(pt_rest);
       PROF_ADD(pc_rest, pt_chunks, pt_rest);
       e++;

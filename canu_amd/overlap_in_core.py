@@ -102,7 +102,8 @@ EXPORTS = ["ovl_params_init", "ovl_params_finalize", "ovl_ctx_create", "ovl_ctx_
            "ovl_ctx_write_ovb", "ovl_ctx_write_stats", "ovl_set_read_libraries",
            "ovl_hash_limits_init", "ovl_build_hash_batch", "ovl_driver_params_init",
            "ovl_overlap_driver", "ovl_seed_hits", "ovl_probe_ceiling", "ovl_probe_replay",
-           "ovl_export_index", "ovl_import_index", "ovl_traceback_window_rows"]
+           "ovl_export_index", "ovl_import_index", "ovl_traceback_window_rows",
+           "ovl_row_end_margin"]
 
 _lib = None
 
@@ -167,6 +168,12 @@ def load_library(path: str | None = None):
 def traceback_window_rows() -> int:
     """Rows per traceback window of the staged extension kernel (a build constant)."""
     return int(load_library().ovl_traceback_window_rows())
+
+
+def row_end_margin() -> int:
+    """Bases from a read's end within which the staged row loop keeps its per-cell end
+    bookkeeping (a build constant)."""
+    return int(load_library().ovl_row_end_margin())
 
 
 @dataclasses.dataclass

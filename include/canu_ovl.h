@@ -280,6 +280,12 @@ void       *ovl_ctx_stream(ovl_ctx *ctx);
  * exported for tests that place alignments around the window edges. */
 int         ovl_traceback_window_rows(void);
 
+/* Bases from either read's end within which a row of the staged extension's row loop keeps
+ * the per-cell end bookkeeping (OVL_END_MARGIN of canu_amd/csrc/ovl_extend.hip); rows further
+ * from both ends skip it.  A build constant, exported for tests that place alignment ends
+ * around it. */
+int         ovl_row_end_margin(void);
+
 /* Measurement only (bench.py's probe roofline; no reference counterpart, ABI 4): the rate
  * of independent random 16-B loads over the CURRENT index table's own allocation
  * (2^tab_bits slots, the table the hash probe looks each query window up in), in G loads/s,
