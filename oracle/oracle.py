@@ -243,6 +243,46 @@ def dump_store(gkp: str, store: str) -> np.ndarray:
         return np.fromfile(out, dtype=RECORD_DTYPE)
 
 
+FE_BIN = os.path.join(HERE, "_ref", "fe_ref")
+
+
+def fe_reference_available() -> bool:
+    """The reference findErrors and what builds its two stores."""
+    return os.path.exists(FE_BIN) and reference_available() and store_available()
+
+
+def run_find_errors(rs, records, bgn: int, end: int, args, binary: str | None = None):
+    """The REFERENCE findErrors (oracle/_ref/fe_ref, the reference's own main()) on reads rs and
+    overlap records, each given once: the gkpStore by build_gkpstore, the overlap store by
+    build_store, the command line canu's (OverlapErrorAdjustment.pm:194-202) with `args`
+    added.  -> (.red bytes, passed, failed, the store's records of [bgn, end] in store order,
+    which is what Read_Olaps loads)."""
+    import re
+    from canu_amd.overlap_in_core import write_ovb  # input writer only
+    binary = binary or FE_BIN
+    if not os.path.exists(binary):
+        raise FileNotFoundError(binary)
+    inp = np.asarray(records, dtype=RECORD_DTYPE)
+    with tempfile.TemporaryDirectory(dir=os.environ.get("TMPDIR", "/tmp")) as d:
+        gkp = build_gkpstore(rs, d)
+        ovb = os.path.join(d, "in.ovb")
+        write_ovb(inp, ovb, counts=False)
+        store = os.path.join(d, "asm.ovlStore")
+        build_store(gkp, store, [ovb])
+        stored = dump_store(gkp, store)
+        red = os.path.join(d, "1.red")
+        cp = subprocess.run([binary, "-G", gkp, "-O", store, "-R", str(bgn), str(end), *args,
+                             "-l", "500", "-o", red, "-t", "4"], capture_output=True, text=True)
+        if cp.returncode != 0:
+            raise RuntimeError(f"findErrors failed ({cp.returncode}): {cp.stderr[-2000:]}")
+        with open(red, "rb") as f:
+            raw = f.read()
+    passed = int(re.search(r"Passed overlaps =\s+(\d+)", cp.stderr).group(1))
+    failed = int(re.search(r"Failed overlaps =\s+(\d+)", cp.stderr).group(1))
+    sel = stored[(stored["a"] >= bgn) & (stored["a"] <= end)]
+    return raw, passed, failed, sel
+
+
 MHAPCONVERT_BIN = os.path.join(HERE, "_ref", "mhapConvert")
 
 

@@ -225,8 +225,12 @@ def _vote(T, col, pos):
         T[pos, col] += 1
 
 
-def analyze_alignment(T, A, a_part, a_len, a_offset, b_part, delta, P):
-    """Analyze_Alignment, findErrors-Analyze_Alignment.C:100-293.  T: the A read's tallies."""
+def analyze_alignment(T, A, a_part, a_len, a_offset, b_part, delta, P, stats=None):
+    """Analyze_Alignment, findErrors-Analyze_Alignment.C:100-293.  T: the A read's tallies.
+    `stats`, if a dict, counts in "outside" the matching-base votes that fall outside the read
+    (the reference writes them to whatever lies there), collects in "runs" the lengths of the
+    match runs that vote when kmer_len < 2 * end_exclude_len (where the first and third vote
+    loops can overlap) and counts in "fs_skipped" the changes :282 keeps from voting."""
     gv = [(-1, -1, A_SUBST)]                                              # frag_sub, align_sub, vote
     i = j = p = 0
 
@@ -262,10 +266,14 @@ def analyze_alignment(T, A, a_part, a_len, a_offset, b_part, delta, P):
         if prev_match >= K:                                               # :246-270
             # the first and third loops exactly as written: with kmer_len < 2 end_exclude_len
             # they overlap, and can step outside the run; outside the read there is no tally
+            if stats is not None and K < 2 * X:
+                stats.setdefault("runs", set()).add((prev_match, c == 1, c == ct, a_offset > 0))
             for q in list(range(0, p_lo)) + list(range(p_hi, prev_match)):
                 k = a_offset + f0 + q + 1
                 if 0 <= k < T.shape[0]:
                     _vote(T, SUBST0 + int(A[k]), k)
+                elif stats is not None:
+                    stats["outside"] = stats.get("outside", 0) + 1
             if p_hi > p_lo:
                 k0 = a_offset + f0 + p_lo + 1
                 k1 = a_offset + f0 + p_hi + 1
@@ -275,6 +283,8 @@ def analyze_alignment(T, A, a_part, a_len, a_offset, b_part, delta, P):
             next_match = gv[c + 1][1] - gv[c][1] - 1
             fs = a_offset + gv[c][0]
             if fs < 0 or fs >= a_len:                                     # :282, a_len: a quirk
+                if stats is not None:
+                    stats["fs_skipped"] = stats.get("fs_skipped", 0) + 1
                 continue
             if prev_match + next_match >= V:
                 col = DELETES if gv[c][2] == DELETE else \
@@ -301,7 +311,8 @@ def make_record(a, b, a_hang, b_hang, flipped):
 
 def find_errors(records, reads: dict, bgn: int, end: int, P: dict, stats=None):
     """Read_Olaps .. Output_Corrections -> (.red records, passed, failed).  reads: id -> bytes.
-    `stats`, if a dict, receives rows and bases aligned."""
+    `stats`, if a dict, receives rows and bases aligned, and the tallies (read -> one row of
+    Vote_Tally_t per base) and degrees (read -> [left, right]) the decision is made from."""
     erate = P["erate"]
     seqs = {}
 
@@ -344,9 +355,12 @@ def find_errors(records, reads: dict, bgn: int, end: int, P: dict, stats=None):
                 stats["rescued"] = stats.get("rescued", 0) + 1
         if errors <= error_bound(olap_len, erate) and to_end:
             passed += 1
-            analyze_alignment(tallies[a], A, a_part, a_end, a_offset, b_part, delta, P)
+            analyze_alignment(tallies[a], A, a_part, a_end, a_offset, b_part, delta, P, stats)
         else:
             failed += 1
+    if stats is not None:
+        stats["tallies"] = tallies
+        stats["degrees"] = deg
     return output_corrections(tallies, deg, seqs, reads, bgn, end, P), passed, failed
 
 
@@ -394,7 +408,7 @@ def output_corrections(tallies, deg, seqs, reads, bgn, end, P):
 # ----------------------------------------------------------------------------- the fixtures
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-FIXTURES = ("a", "b", "c", "d")
+FIXTURES = ("a", "b", "c", "d", "e", "f", "g", "h", "i")
 _golden: dict = {}
 
 

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import fe_restate as FR
+import fe_votes as FV
 import oracle
 from canu_amd import find_errors as FE
 from canu_amd.overlap_in_core import RECORD_DTYPE, write_ovb
@@ -49,6 +50,98 @@ def test_fixtures_cover_the_cases(built):
     o["use_haplo_ct"] = True                          # the haplotype count matters there
     got, _, _ = FR.find_errors(c[1], FR.reads_dict(c[0]), c[5], c[6], o)
     assert got.shape[0] < c[2].shape[0]
+
+
+def _walked(name):
+    """A fixture through the restatement and the instrumented ladders -> (counts, stats, P)."""
+    rs, inp, red, passed, failed, bgn, end, args = FR.golden(name)
+    P = FR.parse_args(args)
+    st = {}
+    reads = FR.reads_dict(rs)
+    got, p, f = FR.find_errors(inp, reads, bgn, end, P, st)
+    again, n = FV.walk(st["tallies"], st["degrees"], reads, bgn, end, P)
+    assert got.tobytes() == again.tobytes() == red.tobytes(), name
+    return n, st, P
+
+
+def test_fixtures_reach_every_branch(built):
+    """Every branch of the two Output_Corrections ladders and every constructed case is in some
+    fixture, so the reference's own bytes back it: fe_votes.REQUIRED, counted by the ladders
+    walked once more with a counter on every branch, whose records equal the reference's."""
+    total = FV.collections.Counter()
+    seen = {}
+    for name in FR.FIXTURES:
+        n, st, P = _walked(name)
+        total.update(n)
+        seen[name] = (n, st, P)
+        if name in FV.LINES:                  # nothing voted outside a read in the constructed ones
+            assert st.get("outside", 0) == 0 and FR.golden(name)[7] == FV.LINES[name]
+    assert not [k for k in FV.REQUIRED if total[k] == 0]
+    # with -x 0 nothing votes for A's own letter (fe_votes' docstring): the one row of the
+    # table that no input reaches
+    assert total["!is_change with -x 0"] == 0
+    assert all(seen[k][2]["end_exclude_len"] == 0 for k in "bgi")
+    # what the single fixtures are for
+    for k in "eh":
+        assert seen[k][0]["insert record"] == 0 and seen[k][0]["haplo_ct >= 2, refused"] > 0
+    assert seen["f"][0]["two records at the last base of a block"] == 1
+    assert seen["g"][0]["ins_haplo_ct >= 2, refused"] > 0
+    assert seen["i"][0]["insert plane at MAX_VOTE"] == 1
+    # kmer_len < 2 * end_exclude_len: runs of K, 2X - 1, 2X and 2X + 1 between two changes, at
+    # the alignment's start and at its end, from overlaps with a_hang > 0 and without
+    n, st, P = seen["h"]
+    K, X = P["kmer_len"], P["end_exclude_len"]
+    assert K < 2 * X and st["fs_skipped"] > 0
+    for r in (K, 2 * X - 1, 2 * X, 2 * X + 1):
+        for hang in (False, True):
+            assert (r, False, False, hang) in st["runs"], (r, hang)
+            assert (r, False, True, hang) in st["runs"], (r, hang)
+        assert (r, True, False, True) in st["runs"], r
+    assert (2 * X - 1, True, False, False) in st["runs"]
+
+
+def _fresh_reference(lab):
+    """The restatement against a fresh run of the reference findErrors on a lab job."""
+    from canu_amd.synth import ReadSet
+    if not oracle.fe_reference_available():               # asked after `built`, which makes it
+        pytest.skip("oracle/_ref/fe_ref, oic_ref and ovs_ref are not built")
+    reads, recs, bgn, end, want, p, f, st = FV.restate(lab)
+    lens = np.array([len(r) for r in reads], dtype=np.uint32)
+    offs = np.zeros(len(reads), dtype=np.uint64)
+    offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+    rs = ReadSet(bases=np.frombuffer(b"".join(reads), dtype=np.uint8).copy(), offsets=offs,
+                 lengths=lens, first_iid=1)
+    raw, rp, rf, sel = oracle.run_find_errors(rs, np.array(recs, dtype=RECORD_DTYPE), bgn, end,
+                                              lab.args)
+    assert sel.shape[0] == len(recs)
+    ref = np.frombuffer(raw, dtype=FR.RED_DTYPE)
+    assert want.tobytes() == ref.tobytes(), FE.dump_red(want[:30]) + "\n" + FE.dump_red(ref[:30])
+    assert (p, f) == (rp, rf)
+    return want
+
+
+@pytest.mark.parametrize("line", sorted(FV.LINES))
+def test_restatement_equals_fresh_reference(built, line):
+    """Random small tallies at 20 sites, three seeds, under each option line."""
+    records = 0
+    for seed in (11, 12, 13):
+        lab = FV.Lab(seed * 100 + ord(line), FV.LINES[line])
+        FV.random_sites(lab, 20)
+        lab.false_pair(0)
+        red = _fresh_reference(lab)
+        records += int(((red["word"] >> 2) & 15 != 0).sum())
+    assert records > 0
+
+
+@pytest.mark.parametrize("plane,line", [
+    ("subst", "f"), ("subst_confirmed_1", "e"), ("confirmed", "e"), ("insert", "i"),
+    ("insert_no_insert_1", "i"), ("no_insert", "g")])
+def test_saturation_equals_fresh_reference(built, plane, line):
+    """255, 256 and 300 votes on every plane of the tally: MAX_VOTE holds each of them."""
+    lab = FV.Lab(77, FV.LINES[line])
+    for n in (255, 256, 300):
+        FV.saturation(lab, plane, n)
+    _fresh_reference(lab)
 
 
 def test_aligner_by_hand():

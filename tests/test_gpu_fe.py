@@ -1,12 +1,14 @@
-"""findErrors on the GPU (libcanu_fe.so): the reference's .red bytes on the four fixtures, and
-the shapes, boundaries and error paths against the Python restatement (tests/fe_restate.py,
-itself pinned to the reference by tests/test_fe_cpu.py)."""
+"""findErrors on the GPU (libcanu_fe.so): the reference's .red bytes on the fixtures, and the
+shapes, boundaries, error paths and constructed vote cases (tests/fe_votes.py) against the
+Python restatement (tests/fe_restate.py, itself pinned to the reference by
+tests/test_fe_cpu.py)."""
 import os
 
 import numpy as np
 import pytest
 
 import fe_restate as FR
+import fe_votes as FV
 from canu_amd import find_errors as FE
 from canu_amd.overlap_in_core import RECORD_DTYPE
 from canu_amd.synth import ReadSet
@@ -266,6 +268,95 @@ def test_saturation(built):
     got, _, _ = _gpu(reads, recs[:300] + recs[300:340], 1, 1, o)   # 255 against 40: a record
     assert got.shape[0] == 2 and int(got[1]["word"]) >> 6 == 120
     assert (int(got[1]["word"]) >> 2) & 15 == FR.A_SUBST + (was + 1) % 4
+
+
+# ------------------------------------------------- the vote and decision ladders, by construction
+
+def _lab_check(lab, order=None):
+    """The lab's preconditions (every site carries the tally it was built for, by the
+    restatement's tallies), then the library against the restatement -> the records."""
+    reads, recs, bgn, end, want, p, f, _ = FV.restate(lab, order)
+    _check(reads, recs, bgn, end, lab.P)
+    return reads, recs, bgn, end, want
+
+
+@pytest.mark.parametrize("line", sorted(FV.LINES))
+@pytest.mark.parametrize("group", sorted(FV.GROUPS))
+def test_vote_cases(built, group, line):
+    """Each group of constructed sites under each option line (fe_votes.LINES)."""
+    lab = FV.Lab(300 + ord(line), FV.LINES[line])
+    FV.GROUPS[group](lab)
+    lab.false_pair(0)
+    _, _, _, _, want = _lab_check(lab)
+    if group in ("substitution", "positions"):
+        assert ((want["word"] >> 2) & 15 != 0).any()
+
+
+@pytest.mark.parametrize("line", sorted(FV.LINES))
+def test_positions_shuffled(built, line):
+    """The votes are atomics: the overlaps in another order give the same bytes."""
+    lab = FV.Lab(300 + ord(line), FV.LINES[line])
+    FV.positions(lab)
+    reads, recs, bgn, end, want = _lab_check(lab)
+    rng = np.random.default_rng(5)
+    for _ in range(2):
+        order = [int(i) for i in rng.permutation(len(recs))]
+        got, _, _ = _gpu(reads, [recs[i] for i in order], bgn, end, lab.P)
+        assert got.tobytes() == want.tobytes()
+    at = set((int(r["readID"]), int(r["word"]) >> 6) for r in want if (int(r["word"]) >> 2) & 15)
+    assert set(j for _, j in at) >= set(FV.POSITIONS) | {0}
+
+
+def test_short_kmer(built):
+    """kmer_len < 2 * end_exclude_len: the first and third vote loops overlap and leave the run."""
+    lab = FV.Lab(41, FV.LINES["h"])
+    FV.short_kmer(lab)
+    FV.substitution(lab)
+    reads, recs, bgn, end, want, _, _, st = FV.restate(lab)
+    K, X = lab.P["kmer_len"], lab.P["end_exclude_len"]
+    assert set(r for r, _, _, _ in st["runs"]) >= {K, 2 * X - 1, 2 * X, 2 * X + 1}
+    assert st["fs_skipped"] > 0 and any(h for _, _, _, h in st["runs"])
+    _check(reads, recs, bgn, end, lab.P)
+
+
+@pytest.mark.parametrize("plane,line", [
+    ("subst", "f"), ("subst_confirmed_1", "e"), ("confirmed", "e"), ("insert", "i"),
+    ("insert_no_insert_1", "i"), ("no_insert", "g")])
+def test_vote_saturation(built, plane, line):
+    """255, 256 and 300 votes on one plane, each next to counts that show whether the plane was
+    held at MAX_VOTE (fe_votes.saturation)."""
+    lab = FV.Lab(78, FV.LINES[line])
+    for n in (255, 256, 300):
+        FV.saturation(lab, plane, n)
+    _lab_check(lab)
+
+
+def test_insert_saturation_flips_the_decision(built):
+    """300 + 200 + 60 inserted letters behind one base: 2 * 300 >= 560 would be no record; held
+    at 255, 2 * 255 < 515 is one."""
+    lab = FV.Lab(79, FV.LINES["i"])
+    FV.insert_flip(lab)
+    a, j, t = lab.want[0]
+    assert t[FR.INSERT0:] == [255, 200, 60, 0]
+    _, _, _, _, want = _lab_check(lab)
+    assert want.shape[0] == 2 and int(want[1]["word"]) >> 6 == j
+    assert (int(want[1]["word"]) >> 2) & 15 == FR.A_INSERT
+
+
+@pytest.mark.parametrize("d", [1, 2, 3, 4, 13, 14, 15])
+def test_degree_thresholds(built, d):
+    """-d at the degree of an end and one above it, on both ends (degrees 1, 2, 3, 13, 14)."""
+    lab = FV.Lab(80, FV.LINES["e"] + ["-d", str(d)])
+    FV.degrees(lab)
+    _, _, _, _, want = _lab_check(lab)
+    assert len(set(int(w) & 3 for w in want["word"])) > 1 or d in (1, 15)
+
+
+@pytest.mark.parametrize("line", sorted(FV.LINES))
+def test_random_tallies(built, line):
+    lab = FV.Lab(900 + ord(line), FV.LINES[line])
+    FV.random_sites(lab, 20)
+    _lab_check(lab)
 
 
 def test_range_and_error_behaviour(built):

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Write tests/golden/fe_*.npz from the reference findErrors.
 
-    tools/make_fe_golden.py --findErrors PATH [--out tests/golden]
+    tools/make_fe_golden.py [--findErrors PATH] [--out tests/golden]
 
-The binary is built by hand from the reference sources, outside this tree (DESIGN.md,
-"Reference binary for findErrors"); nothing of it is committed.  Reads and overlaps come from
+The binary is oracle/_ref/fe_ref, which `make -C oracle` compiles from the reference sources
+where they lie ("Reference binary for findErrors"); nothing of it is committed.  Reads and overlaps come from
 fixed seeds; the gkpStore is written by the reference's own gkStore code
 (oracle.build_gkpstore), the overlap store by its own ovStore writer (oracle.build_store), and
-the command line is canu's (OverlapErrorAdjustment.pm:194-202).  Each fixture holds the reads,
+the command line is canu's (OverlapErrorAdjustment.pm:194-202).  Fixtures e..i are the
+constructed vote cases of tests/fe_votes.py, one option line each.  Each fixture holds the reads,
 the store's records of the range (what Read_Olaps loads), the reference's .red bytes, its
 passed / failed counts, the range and the options.
 """
@@ -15,8 +16,6 @@ from __future__ import annotations
 
 import argparse
 import os
-import re
-import subprocess
 import sys
 import tempfile
 
@@ -28,6 +27,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fe_restate as FR  # noqa: E402
+import fe_votes as FV  # noqa: E402
 
 _ACGT = b"ACGT"
 _COMP = bytes.maketrans(b"ACGTN", b"TGCAN")
@@ -260,7 +260,46 @@ def fixture_d():
     return S.reads, recs, 3, last_in_range, ["-e", "0.06"]
 
 
-FIXTURES = [("a", fixture_a), ("b", fixture_b), ("c", fixture_c), ("d", fixture_d)]
+def lab_fixture(name: str):
+    """Fixtures e..i: the constructed vote cases of tests/fe_votes.py, one option line each."""
+    def mk():
+        lab = FV.fixture(name)
+        FV.restate(lab)                       # every site carries the tally it was built for
+        reads, recs, bgn, end = lab.job()
+        return reads, recs, bgn, end, lab.args
+    return mk
+
+
+FIXTURES = [("a", fixture_a), ("b", fixture_b), ("c", fixture_c), ("d", fixture_d)] + \
+    [(n, lab_fixture(n)) for n in "efghi"]
+
+
+def lab_assertions(name: str, red) -> None:
+    """What each of e..i is there for, counted on the reference's own records."""
+    t = (red["word"] >> 2) & 15
+    pos = red["word"] >> 6
+    rec = red[t != 0]
+    key = rec["readID"].astype(np.uint64) << np.uint64(32) | (rec["word"] >> 6)
+    _, n = np.unique(key, return_counts=True)
+    two = int((n == 2).sum())                              # bases with two records
+    ins = int((t >= FR.A_INSERT).sum())
+    at = set(int(v) for v in pos[t != 0])
+    assert at >= {254, 255, 256, 257, 511, 512}, (name, sorted(at))
+    keep = red["word"][t == 0] & 3
+    assert set(int(v) for v in keep) == {0, 1, 2, 3}, (name, "degrees on both sides of -d")
+    if name in "eh":        # no insert record is possible: the haplotype count refuses them
+        assert ins == 0 and two == 0 and (t == FR.DELETE).any(), (name, ins, two)
+    if name == "f":         # substitution + insert and delete + insert at one base
+        assert two >= 10 and ins == two, (name, ins, two)
+        d = rec[(rec["word"] >> 2) & 15 == FR.DELETE]
+        dk = set((int(r["readID"]), int(r["word"]) >> 6) for r in d)
+        ik = set((int(r["readID"]), int(r["word"]) >> 6) for r in rec
+                 if (int(r["word"]) >> 2) & 15 >= FR.A_INSERT)
+        assert len(dk & ik) >= 2, (name, "delete and insert records at one base")
+    if name in "gi":        # inserts through `confirmed`, never next to another record
+        assert ins >= 5 and two == 0, (name, ins, two)
+    if name == "i":
+        assert ins > 5, name
 
 
 def read_set(reads: list[bytes]):
@@ -273,35 +312,12 @@ def read_set(reads: list[bytes]):
                    lengths=lens, first_iid=1)
 
 
-def parse_counts(stderr: str):
-    p = re.search(r"Passed overlaps =\s+(\d+)", stderr)
-    f = re.search(r"Failed overlaps =\s+(\d+)", stderr)
-    return int(p.group(1)), int(f.group(1))
-
-
-def run_reference(binary: str, reads, recs, bgn, end, args, keep_store=None):
+def run_reference(binary, reads, recs, bgn, end, args):
     import oracle
-    from canu_amd.overlap_in_core import RECORD_DTYPE, write_ovb
+    from canu_amd.overlap_in_core import RECORD_DTYPE
     rs = read_set(reads)
-    inp = np.array(recs, dtype=RECORD_DTYPE)
-    with tempfile.TemporaryDirectory() as d:
-        gkp = oracle.build_gkpstore(rs, d)
-        ovb = os.path.join(d, "in.ovb")
-        write_ovb(inp, ovb, counts=False)
-        store = os.path.join(d, "asm.ovlStore")
-        oracle.build_store(gkp, store, [ovb])
-        stored = oracle.dump_store(gkp, store)
-        red = os.path.join(d, "1.red")
-        line = ["-G", gkp, "-O", store, "-R", str(bgn), str(end), *args, "-l", "500",
-                "-o", red, "-t", "4"]
-        p = subprocess.run([binary, *line], capture_output=True, text=True)
-        if p.returncode != 0:
-            raise RuntimeError(f"findErrors failed ({p.returncode}): {p.stderr[-2000:]}")
-        raw = open(red, "rb").read()
-        if keep_store is not None:
-            keep_store(d, gkp, store, stored)
-    passed, failed = parse_counts(p.stderr)
-    sel = stored[(stored["a"] >= bgn) & (stored["a"] <= end)]
+    raw, passed, failed, sel = oracle.run_find_errors(rs, np.array(recs, dtype=RECORD_DTYPE),
+                                                      bgn, end, args, binary=binary)
     return rs, sel, raw, passed, failed
 
 
@@ -335,7 +351,7 @@ def store_fixture(out_dir: str) -> None:
 
 def main() -> int:
     ap = argparse.ArgumentParser()
-    ap.add_argument("--findErrors", required=True)
+    ap.add_argument("--findErrors", default=os.path.join(ROOT, "oracle", "_ref", "fe_ref"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)
@@ -351,6 +367,8 @@ def main() -> int:
         assert passed > 0 and failed > 0, (name, passed, failed)
         ids, n = np.unique(red["readID"], return_counts=True)
         assert ids.shape[0] == end - bgn + 1 and (n == 1).any(), name
+        if name in "efghi":
+            lab_assertions(name, red)
         if name == "d":
             keep = red["word"][t == 0] & 3
             assert set(int(v) & 1 for v in keep) == {0, 1}, "keep_left takes one value"
