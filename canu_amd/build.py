@@ -241,6 +241,48 @@ def build_fe_cli(force: bool = False, verbose: bool = True) -> str:
     return FE_CLI_OUT
 
 
+CO_OUT = os.path.join(OUT_DIR, "libcanu_co.so")
+CO_DEPS = [os.path.join(CSRC, "co.hip"), os.path.join(HERE, "..", "include", "canu_co.h"),
+           os.path.join(HERE, "..", "include", "canu_fe.h"),
+           os.path.join(HERE, "..", "include", "canu_ovl.h")]
+CO_CLI_OUT = os.path.join(BIN_DIR, "correctOverlaps")
+
+
+def build_co(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_co.so: correctOverlaps, overlap error rates from corrected reads."""
+    if not force and not _stale(CO_OUT, CO_DEPS):
+        return CO_OUT
+    os.makedirs(OUT_DIR, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, *HIPCC_FLAGS, "-o", CO_OUT + ".tmp", os.path.join(CSRC, "co.hip")]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(CO_OUT + ".tmp", CO_OUT)
+    return CO_OUT
+
+
+def build_co_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/correctOverlaps: the command line canu's oea.sh runs (host C++ over
+    libcanu_co.so, found next to it through the rpath)."""
+    lib = build_co(verbose=verbose)
+    src = os.path.join(CSRC, "co_main.cpp")
+    deps = [src, lib, os.path.join(CSRC, "gkp_store.h"), os.path.join(CSRC, "ovs_reader.h"),
+            os.path.join(CSRC, "co_files.h"), *CO_DEPS[1:]]
+    if not force and not _stale(CO_CLI_OUT, deps):
+        return CO_CLI_OUT
+    os.makedirs(BIN_DIR, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
+           "-o", CO_CLI_OUT + ".tmp", src, "-L" + OUT_DIR, "-lcanu_co",
+           "-Wl,-rpath,$ORIGIN/../lib", "-Wl,--allow-shlib-undefined"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(CO_CLI_OUT + ".tmp", CO_CLI_OUT)
+    return CO_CLI_OUT
+
+
 def build(force: bool = False, verbose: bool = True, profile: bool = False) -> str:
     """profile=True builds the instrumented variant (in-kernel cycle stamps, OVL_DEBUG=1
     prints them) as libcanu_ovl_prof.so; load it with CANU_OVL_LIB."""
@@ -270,3 +312,5 @@ if __name__ == "__main__":
         build_pair_cli(force="--force" in sys.argv)
         build_fe(force="--force" in sys.argv)
         build_fe_cli(force="--force" in sys.argv)
+        build_co(force="--force" in sys.argv)
+        build_co_cli(force="--force" in sys.argv)
