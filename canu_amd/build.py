@@ -283,6 +283,47 @@ def build_co_cli(force: bool = False, verbose: bool = True) -> str:
     return CO_CLI_OUT
 
 
+FS_OUT = os.path.join(OUT_DIR, "libcanu_fs.so")
+FS_DEPS = [os.path.join(CSRC, "fs.hip"), os.path.join(CSRC, "fs_fasta.h"),
+           os.path.join(HERE, "..", "include", "canu_fs.h")]
+FS_CLI_OUT = os.path.join(BIN_DIR, "falconsense")
+
+
+def build_fs(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_fs.so: falconsense, corrected reads from correction layouts."""
+    if not force and not _stale(FS_OUT, FS_DEPS):
+        return FS_OUT
+    os.makedirs(OUT_DIR, exist_ok=True)
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, *HIPCC_FLAGS, "-o", FS_OUT + ".tmp", os.path.join(CSRC, "fs.hip")]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(FS_OUT + ".tmp", FS_OUT)
+    return FS_OUT
+
+
+def build_fs_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/falconsense: the command line canu's correctReads.sh runs (host C++ over
+    libcanu_fs.so, found next to it through the rpath)."""
+    lib = build_fs(verbose=verbose)
+    src = os.path.join(CSRC, "fs_main.cpp")
+    deps = [src, lib, os.path.join(CSRC, "gkp_store.h"), os.path.join(CSRC, "tgs_reader.h"),
+            *FS_DEPS[1:]]
+    if not force and not _stale(FS_CLI_OUT, deps):
+        return FS_CLI_OUT
+    os.makedirs(BIN_DIR, exist_ok=True)
+    cxx = os.environ.get("CXX", "g++")
+    cmd = [cxx, "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "..", "include"),
+           "-o", FS_CLI_OUT + ".tmp", src, "-L" + OUT_DIR, "-lcanu_fs",
+           "-Wl,-rpath,$ORIGIN/../lib", "-Wl,--allow-shlib-undefined"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True, cwd=CSRC)
+    os.replace(FS_CLI_OUT + ".tmp", FS_CLI_OUT)
+    return FS_CLI_OUT
+
+
 def build(force: bool = False, verbose: bool = True, profile: bool = False) -> str:
     """profile=True builds the instrumented variant (in-kernel cycle stamps, OVL_DEBUG=1
     prints them) as libcanu_ovl_prof.so; load it with CANU_OVL_LIB."""
@@ -314,3 +355,5 @@ if __name__ == "__main__":
         build_fe_cli(force="--force" in sys.argv)
         build_co(force="--force" in sys.argv)
         build_co_cli(force="--force" in sys.argv)
+        build_fs(force="--force" in sys.argv)
+        build_fs_cli(force="--force" in sys.argv)

@@ -1,0 +1,1232 @@
+// fs.hip -- libcanu_fs.so: canu's falconsense (src/correction/falconsense.C, falconConsensus*.C)
+// on gfx950.  include/canu_fs.h says what is reproduced; this is how.
+//
+//   k_fs_locate     one wave per evidence read: edlib's EDLIB_MODE_HW result in closed form.  An
+//                   infix pass gives the distance and the first best end column, a prefix pass
+//                   of the reversed query over the reversed target up to that column gives the
+//                   longest start; then the two rejection tests of alignReadsToTemplate.
+//   k_fs_path       one wave per surviving evidence read: obtainAlignment's recursion with an
+//                   explicit stack in LDS.  A split runs the left half and the reversed right
+//                   half, keeps Pv / Mv and the end score of every 64-row block of the two last
+//                   columns, and takes the first row r with L[r] + R[r+1] == best as a wave-wide
+//                   first match, then the two boundary rules.  A leaf keeps Pv / Mv / the block
+//                   score of every column -- under FS_LEAF_BYTES by the leaf rule, so the
+//                   scratch of a wave is fixed -- and walks up / left / diagonal from the
+//                   corner.  The leaf's operations (one byte each, backwards) go through a
+//                   per-wave buffer; tags are then made 64 operations at a time with ballots
+//                   and written with their place in (evidence, tag) order.  Alignment strings
+//                   are never made.
+//   hipcub          a segmented radix sort of each template's tags by (t_pos, delta, base,
+//                   link); the sort is stable, so a run's first value is its first appearance.
+//   k_fs_consensus  one wave per template: coverage, links (runs) and columns (runs of runs),
+//                   the predecessor column of every link by binary search, the scan over the
+//                   columns in (t_pos, delta, base) order, the walk back and the case rule.
+//
+// The scan in integers: a link scores link_count - coverage * 0.5 plus the score of its
+// predecessor column, so every score is a multiple of 0.5 and twice the score is an exact
+// integer.  The reference starts every maximum at DBL_MIN, the smallest positive double: it
+// vanishes in a sum with any nonzero multiple of 0.5, 0 + DBL_MIN is not greater than DBL_MIN,
+// so DBL_MIN is 0 here and "greater than DBL_MIN" is "greater than 0" (tests/test_fs_cpu.py
+// compares the two forms).
+//
+// The aligner core (dp_pass) is that of pair.hip: Myers' bit-vector recurrence, lane b holding
+// rows 64b..64b+63, columns as a skewed wavefront, 4096-row stripes.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/canu_fs.h"
+#include "fs_fasta.h"
+
+namespace {
+
+thread_local std::string g_err;
+
+int fail(int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+#define HIP_TRY(x)                                                                  \
+  do {                                                                              \
+    hipError_t e_ = (x);                                                            \
+    if (e_ != hipSuccess)                                                           \
+      return fail(e_ == hipErrorOutOfMemory ? FS_ERR_OOM : FS_ERR_HIP, "%s: %s", #x, \
+                  hipGetErrorString(e_));                                           \
+  } while (0)
+
+constexpr int WAVES_PER_BLOCK = 4;
+constexpr int STRIPE_ROWS = 4096;                     // 64 lanes x 64 rows
+constexpr int LDS_COLUMNS = 16384;                    // stripe-boundary row kept in LDS
+constexpr int LDS_WORDS = LDS_COLUMNS / 16;           // 2 bits per column
+constexpr int LEAF_ENTRIES = FS_LEAF_BYTES / 20 + 1;  // block columns of a leaf
+constexpr int STACK_DEPTH = 40;                       // the target halves at every level
+constexpr uint32_t MAX_READLEN = (1u << 21) - 1;      // AS_MAX_READLEN
+
+enum : int { OP_MATCH = 0, OP_INSERT = 1, OP_DELETE = 2, OP_MISMATCH = 3 };   // EDLIB_EDOP_*
+// the base of a tag and of its predecessor: A C G T N - and '.', the first tag's predecessor
+enum : int { CH_N = 4, CH_GAP = 5, CH_NONE = 6 };
+
+// A tag as a sort key: t_pos at bit 43 (21 bits), delta at 27 (16), slot at 24 (3), prel at 19
+// (2), p_delta at 3 (16), p_ch at 0 (3); bits 21..23 stay 0.
+// slot is the base's column (N and '-' share 4); prel says where the predecessor sits: 0 none
+// (p_t_pos -1), 1 at t_pos - 1, 2 at t_pos -- a predecessor is never anywhere else.
+constexpr int KEY_COL_SHIFT = 21;                     // key >> 21 names the column
+constexpr uint64_t KEY_NONE = ~0ull;
+
+struct Ev {                  // one evidence read of one layout, template included
+  uint64_t seq;              // its first base in the fwd or the rc array
+  uint64_t tag_off;          // its tags
+  uint32_t tag_cap;
+  uint32_t rc;
+  uint32_t tmpl;             // index of its template in the batch
+  int32_t qlen;              // trimmed and cut to the template
+  int32_t wb, we;            // the window of the template it is aligned to
+  int32_t tol;
+  int32_t pad;
+};
+
+struct Loc {
+  int32_t dist, start, end, ok;
+};
+
+struct Tp {                  // one template of the batch
+  uint64_t seq;              // in the fwd array
+  uint64_t tag_off;          // its evidence reads' tags, contiguous
+  uint64_t cov_off;
+  uint64_t out_off;          // 2 * len bytes
+  uint32_t tag_cap;
+  int32_t len;
+};
+
+// ------------------------------------------------------------------ read encoding
+
+__global__ void k_fs_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
+                            const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ len,
+                            uint32_t nreads, uint8_t *__restrict__ fwd, uint8_t *__restrict__ rc,
+                            uint32_t *__restrict__ bad) {
+  for (uint32_t r = blockIdx.x; r < nreads; r += gridDim.x) {
+    const uint8_t *s = bases + src_off[r];
+    const uint64_t d = dst_off[r];
+    const uint32_t L = len[r];
+    for (uint32_t i = threadIdx.x; i < L; i += blockDim.x) {
+      const uint8_t ch = s[i];
+      uint8_t c = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
+      if (c == 4 && ch != 'N') atomicOr(bad, 1u);
+      fwd[d + i] = c;
+      rc[d + (L - 1 - i)] = c < 4 ? (uint8_t)(3 - c) : c;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ the aligner
+
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+__device__ __forceinline__ int dpp_from_lower(int v, int lane0) {   // lane l <- v[l-1]
+  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xf, 0xf, false);
+}
+
+struct Seq {                 // a span of an oriented read, read forwards or backwards
+  const uint8_t *p;
+  int n;
+  int rev;                   // element i is p[n-1-i]
+  __device__ __forceinline__ int at(int i) const { return p[rev ? n - 1 - i : i]; }
+};
+
+struct PassOut {
+  int best, bestcol;         // minimum of the bottom row, the first column attaining it
+  int lastcol;               // last column whose bottom-row score == want (-1: none)
+  int fin;                   // bottom-row score at the last column
+};
+
+// What a pass leaves behind besides its bottom row.  Block g is rows 64g..64g+63.
+struct Keep {
+  uint64_t *colP, *colM;     // leaf: Pv / Mv of block g after column j at [g * n + j]
+  int *colS;                 //       and the score of the block's last row there
+  uint64_t *endP, *endM;     // split: Pv / Mv of block g after the last column at [g]
+  int *endS;                 //        and the score of the block's last row there
+};
+
+// Bottom row of the edit-distance matrix of q (rows) against t (columns); top_hin 0 lets an
+// alignment start at any column (infix), 1 charges every skipped target base (prefix, global).
+// Needs q.n >= 1, t.n >= 1.  Every lane of the wave is in, with the same arguments.
+__device__ PassOut dp_pass(const Seq q, const Seq t, const int top_hin, const int want,
+                           uint32_t *lrow, uint32_t *grow, const Keep keep) {
+  const int lane = threadIdx.x & 63;
+  const int m = q.n, n = t.n;
+  const int nstripes = (m + STRIPE_ROWS - 1) / STRIPE_ROWS;
+  const bool use_g = n > LDS_COLUMNS;
+  int best = INT_MAX, bestcol = -1, lastcol = -1, sc = m;
+  int lb = 0;
+  for (int st = 0; st < nstripes; st++) {
+    const int r0 = st * STRIPE_ROWS;
+    const int rows = min(STRIPE_ROWS, m - r0);
+    const int nb = (rows + 63) >> 6;
+    const bool last = st == nstripes - 1;
+    lb = nb - 1;
+    uint64_t pe0 = 0, pe1 = 0, pe2 = 0, pe3 = 0, pe4 = 0;
+    for (int c = 0; c < nb; c++) {
+      const int i = r0 + c * 64 + lane;
+      const int code = i < m ? q.at(i) : 7;
+      const uint64_t b0 = __ballot(code == 0), b1 = __ballot(code == 1),
+                     b2 = __ballot(code == 2), b3 = __ballot(code == 3),
+                     b4 = __ballot(code == 4);
+      if (lane == c) { pe0 = b0; pe1 = b1; pe2 = b2; pe3 = b3; pe4 = b4; }
+    }
+    uint64_t Pv = ~0ull, Mv = 0;
+    const bool trk = last && lane == lb;
+    // the last row of this lane's block, whose score the lane follows along the columns (the
+    // boundary column holds row + 1)
+    const int lrow_abs = min(r0 + 64 * (lane + 1), m) - 1;
+    const int rr = lane < nb ? (lrow_abs & 63) : 63;
+    sc = lrow_abs + 1;
+    const size_t gblk = (size_t)(st * 64 + lane);
+    int x = 1;                                  // (hout + 1) | base << 2, handed to lane + 1
+    uint32_t cur = lane < n ? (uint32_t)t.at(lane) : 4u;
+    uint32_t nxt = 64 + lane < n ? (uint32_t)t.at(64 + lane) : 4u;
+    uint32_t hw = 0, acc = 0;
+    const int nsteps = n + nb - 1;
+    for (int s = 0; s < nsteps; s++) {
+      if ((s & 63) == 0 && s > 0) {
+        cur = nxt;
+        const int c = s + 64 + lane;
+        nxt = c < n ? (uint32_t)t.at(c) : 4u;
+      }
+      const int base0 = __builtin_amdgcn_readlane((int)cur, s & 63);
+      int hin0 = top_hin;
+      if (st > 0) {
+        if ((s & 15) == 0 && s < n) hw = use_g ? grow[s >> 4] : lrow[s >> 4];
+        hin0 = (int)((hw >> (2 * (s & 15))) & 3u) - 1;
+      }
+      const int xin = dpp_from_lower(x, (hin0 + 1) | (base0 << 2));
+      const int j = s - lane;
+      const bool act = lane < nb && j >= 0 && j < n;
+      int d = 0;
+      if (act) {
+        const int hin = (xin & 3) - 1;
+        const int b = xin >> 2;
+        const uint64_t s0 = 0 - (uint64_t)(b & 1), s1 = 0 - (uint64_t)((b >> 1) & 1),
+                       s2 = 0 - (uint64_t)(b >> 2);
+        const uint64_t e01 = (pe0 & ~s0) | (pe1 & s0), e23 = (pe2 & ~s0) | (pe3 & s0);
+        const uint64_t e03 = (e01 & ~s1) | (e23 & s1);
+        uint64_t Eq = (e03 & ~s2) | (pe4 & s2);
+        const uint64_t neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
+        const uint64_t Xv = Eq | Mv;
+        Eq |= neg;
+        const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
+        uint64_t Ph = Mv | ~(Xh | Pv);
+        uint64_t Mh = Pv & Xh;
+        d = (int)((Ph >> 63) & 1) - (int)((Mh >> 63) & 1);
+        sc += (int)((Ph >> rr) & 1) - (int)((Mh >> rr) & 1);
+        Ph = (Ph << 1) | pos;
+        Mh = (Mh << 1) | neg;
+        Pv = Mh | ~(Xv | Ph);
+        Mv = Ph & Xv;
+        if (trk) {
+          if (sc < best) { best = sc; bestcol = j; }
+          if (sc == want) lastcol = j;
+        }
+        if (keep.colP) {
+          const size_t at = gblk * (size_t)n + (size_t)j;
+          keep.colP[at] = Pv;
+          keep.colM[at] = Mv;
+          keep.colS[at] = sc;
+        }
+        if (!last && lane == lb) {              // lane 63: the next stripe's top boundary
+          acc |= (uint32_t)(d + 1) << (2 * (j & 15));
+          if ((j & 15) == 15 || j == n - 1) {
+            if (use_g) grow[j >> 4] = acc; else lrow[j >> 4] = acc;
+            acc = 0;
+          }
+        }
+      }
+      x = (d + 1) | (xin & ~3);
+    }
+    if (keep.endP && lane < nb) {
+      keep.endP[gblk] = Pv;
+      keep.endM[gblk] = Mv;
+      keep.endS[gblk] = sc;
+    }
+    if (!last) __threadfence();                 // lane 63's row is read by every lane next
+  }
+  PassOut o;
+  o.best = __shfl(best, lb);
+  o.bestcol = __shfl(bestcol, lb);
+  o.lastcol = __shfl(lastcol, lb);
+  o.fin = __shfl(sc, lb);
+  return o;
+}
+
+// Score of row r (0 <= r < m) from the block's end score and its Pv / Mv: the rows above the
+// block's last row down to r + 1 are taken back.
+__device__ __forceinline__ int row_score(const uint64_t P, const uint64_t M, const int end_score,
+                                         const int r, const int m) {
+  const int b = r >> 6;
+  const int lastbit = (min(64 * (b + 1), m) - 1) & 63;
+  const uint64_t upto = lastbit == 63 ? ~0ull : ((1ull << (lastbit + 1)) - 1);
+  const uint64_t above = (r & 63) == 63 ? 0ull : (~0ull << ((r & 63) + 1));
+  const uint64_t hi = above & upto;
+  return end_score - __popcll(P & hi) + __popcll(M & hi);
+}
+
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
+void k_fs_locate(const uint8_t *__restrict__ fwd, const uint8_t *__restrict__ rcs,
+                 const Ev *__restrict__ evs, const Tp *__restrict__ tps, const uint32_t n_ev,
+                 Loc *__restrict__ loc, unsigned long long *__restrict__ cells,
+                 uint32_t *__restrict__ scratch, const uint64_t scratch_words,
+                 const double max_difference) {
+  __shared__ uint32_t s_row[WAVES_PER_BLOCK][LDS_WORDS];
+  const int wave = uni((int)(threadIdx.x >> 6));
+  const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;
+  const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
+  uint32_t *grow = scratch ? scratch + gw * scratch_words : nullptr;
+  const Keep none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (uint32_t e = (uint32_t)gw; e < n_ev; e += n_waves) {
+    const Ev ev = evs[e];
+    const int m = uni(ev.qlen), wb = uni(ev.wb), n = uni(ev.we) - wb;
+    const uint8_t *qp = (uni((int)ev.rc) ? rcs : fwd) + ev.seq;
+    const uint8_t *tp = fwd + tps[ev.tmpl].seq + wb;
+    const PassOut f = dp_pass(Seq{qp, m, 0}, Seq{tp, n, 0}, 0, INT_MIN, s_row[wave], grow, none);
+    unsigned long long c = (unsigned long long)m * n;
+    const int best = uni(f.best), end = uni(f.bestcol);
+    Loc o{best, 0, end, 0};
+    if (best <= uni(ev.tol)) {
+      // the last column of the reversed prefix pass still at `best` is the longest alignment
+      const PassOut r = dp_pass(Seq{qp, m, 1}, Seq{tp, end + 1, 1}, 1, best, s_row[wave], grow, none);
+      c += (unsigned long long)m * (end + 1);
+      o.start = end - uni(r.lastcol);
+      // alignDiff = editDistance / (double)(end - start): one short of the span, as there
+      const double diff = (double)best / (double)(end - o.start);
+      o.ok = diff >= max_difference ? 0 : 1;
+    }
+    loc[e] = o;
+    cells[e] = c;
+  }
+}
+
+// ------------------------------------------------------------------ the path and the tags
+
+struct TagState {            // getAlignTags' running values, the same in every lane
+  int qi;                    // query bases consumed
+  int tj;                    // target bases consumed
+  int jj;                    // insertions since the last target base
+  int p_j, p_jj, p_ch;       // the last tag written
+  uint32_t ntags;
+};
+
+__device__ __forceinline__ uint64_t tag_key(int j, int jj, int ch, int p_j, int p_jj, int p_ch) {
+  const int slot = ch < 4 ? ch : 4;
+  const int prel = p_j < 0 ? 0 : (p_j == j ? 2 : 1);
+  return ((uint64_t)j << 43) | ((uint64_t)jj << 27) | ((uint64_t)slot << 24) |
+         ((uint64_t)prel << 19) | ((uint64_t)p_jj << 3) | (uint64_t)p_ch;
+}
+
+// `count` operations in alignment order -- op_at(i) in every lane -- become tags.  tbgn is the
+// template position of the alignment's first target base, tlen its number of target bases:
+// insertions before the first and after the last target base are the gaps alignReadsToTemplate
+// strips.
+template <class OpAt>
+__device__ void emit_tags(TagState &S, const int count, OpAt op_at, const uint8_t *qp,
+                          const int qlen, const int tbgn, const int tlen, uint64_t *__restrict__ keys,
+                          uint32_t *__restrict__ vals, const uint32_t val0, const uint32_t cap) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t lt = (1ull << lane) - 1;
+  for (int c0 = 0; c0 < count; c0 += 64) {
+    const int cnt = min(64, count - c0);
+    const bool valid = lane < cnt;
+    const int op = valid ? op_at(c0 + lane) : OP_MATCH;
+    const bool isq = valid && op != OP_DELETE, ist = valid && op != OP_INSERT;
+    const uint64_t qmask = __ballot(isq), tmask = __ballot(ist);
+    const int qidx = S.qi + __popcll(qmask & lt);
+    const int tcons = S.tj + __popcll(tmask & lt) + (ist ? 1 : 0);
+    const int j = tbgn - 1 + tcons;
+    const uint64_t tbelow = tmask & lt;
+    int jj = 0;
+    if (!ist) jj = tbelow ? lane - (63 - __clzll(tbelow)) : S.jj + lane + 1;
+    const int ch = isq ? (int)qp[min(qidx, qlen - 1)] : CH_GAP;
+    // jj >= 65535 is skipped there and never becomes a predecessor, so p_jj never reaches it
+    const bool emit = valid && !(op == OP_INSERT && (tcons == 0 || tcons == tlen)) && jj < 65535;
+    const uint64_t emask = __ballot(emit);
+    const uint64_t ebelow = emask & lt;
+    const int src = ebelow ? 63 - __clzll(ebelow) : 0;
+    int p_j = __shfl(j, src), p_jj = __shfl(jj, src), p_ch = __shfl(ch, src);
+    if (!ebelow) { p_j = S.p_j; p_jj = S.p_jj; p_ch = S.p_ch; }
+    const uint32_t at = S.ntags + (uint32_t)__popcll(ebelow);
+    if (emit && at < cap) {
+      keys[at] = tag_key(j, jj, ch, p_j, p_jj, p_ch);
+      vals[at] = val0 + at;
+    }
+    if (emask) {
+      const int lastl = 63 - __clzll(emask);
+      S.p_j = __shfl(j, lastl);
+      S.p_jj = __shfl(jj, lastl);
+      S.p_ch = __shfl(ch, lastl);
+      S.ntags += (uint32_t)__popcll(emask);
+    }
+    S.qi += __popcll(qmask);
+    S.tj += __popcll(tmask);
+    S.jj = tmask ? cnt - 1 - (63 - __clzll(tmask)) : S.jj + cnt;
+  }
+}
+
+struct PathScratch {
+  uint64_t *colP, *colM;     // LEAF_ENTRIES each
+  int *colS;
+  uint64_t *endP, *endM;     // 2 * blocks each: the left pass, then the right pass
+  int *endS;
+  uint8_t *ops;              // a leaf's operations, last first
+  uint32_t *grow;
+};
+
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
+void k_fs_path(const uint8_t *__restrict__ fwd, const uint8_t *__restrict__ rcs,
+               const Ev *__restrict__ evs, const Tp *__restrict__ tps, const uint32_t n_ev,
+               const Loc *__restrict__ loc, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
+               uint32_t *__restrict__ ntags_out, unsigned long long *__restrict__ cells,
+               uint32_t *__restrict__ nleaf_out, uint32_t *__restrict__ nsplit_out,
+               uint64_t *__restrict__ colP_all, uint64_t *__restrict__ colM_all,
+               int *__restrict__ colS_all, uint64_t *__restrict__ endP_all,
+               uint64_t *__restrict__ endM_all, int *__restrict__ endS_all,
+               uint8_t *__restrict__ ops_all, uint32_t *__restrict__ grow_all,
+               const uint32_t max_blocks, const uint64_t ops_bytes, const uint64_t grow_words) {
+  __shared__ uint32_t s_row[WAVES_PER_BLOCK][LDS_WORDS];
+  __shared__ int s_stack[WAVES_PER_BLOCK][STACK_DEPTH][5];
+  const int lane = threadIdx.x & 63;
+  const int wave = uni((int)(threadIdx.x >> 6));
+  const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;
+  const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
+  PathScratch W;
+  W.colP = colP_all + gw * LEAF_ENTRIES;
+  W.colM = colM_all + gw * LEAF_ENTRIES;
+  W.colS = colS_all + gw * LEAF_ENTRIES;
+  W.endP = endP_all + gw * 2 * max_blocks;
+  W.endM = endM_all + gw * 2 * max_blocks;
+  W.endS = endS_all + gw * 2 * max_blocks;
+  W.ops = ops_all + gw * ops_bytes;
+  W.grow = grow_words ? grow_all + gw * grow_words : nullptr;
+  int (*stack)[5] = s_stack[wave];
+
+  for (uint32_t e = (uint32_t)gw; e < n_ev; e += n_waves) {
+    const Loc L = loc[e];
+    if (!uni(L.ok)) {
+      if (lane == 0) { ntags_out[e] = 0; nleaf_out[e] = 0; nsplit_out[e] = 0; }
+      continue;
+    }
+    const Ev ev = evs[e];
+    const int qlen = uni(ev.qlen);
+    const int start = uni(L.start), tlen = uni(L.end) - start + 1;
+    const int tbgn = uni(ev.wb) + start;
+    const uint8_t *qp = (uni((int)ev.rc) ? rcs : fwd) + ev.seq;
+    const uint8_t *tp = fwd + tps[ev.tmpl].seq + tbgn;
+    uint64_t *ek = keys + ev.tag_off;
+    uint32_t *evl = vals + ev.tag_off;
+    const uint32_t val0 = (uint32_t)(ev.tag_off - tps[ev.tmpl].tag_off);
+    const uint32_t cap = ev.tag_cap;
+    TagState S{0, 0, 0, -1, 0, CH_NONE, 0};
+    unsigned long long c = 0;
+    uint32_t nleaf = 0, nsplit = 0;
+
+    int sp = 0;
+    if (lane == 0) {
+      stack[0][0] = 0; stack[0][1] = qlen; stack[0][2] = 0; stack[0][3] = tlen;
+      stack[0][4] = uni(L.dist);
+    }
+    sp = 1;
+    __builtin_amdgcn_wave_barrier();
+    while (sp > 0) {
+      sp--;
+      const int q0 = uni(stack[sp][0]), qn = uni(stack[sp][1]), t0 = uni(stack[sp][2]),
+                tn = uni(stack[sp][3]), best = uni(stack[sp][4]);
+      if (qn == 0 || tn == 0) {
+        // an empty side: every remaining base is a DELETE (no query) or an INSERT (no target)
+        const int op = qn == 0 ? OP_DELETE : OP_INSERT;
+        emit_tags(S, qn + tn, [op](int) { return op; }, qp, qlen, tbgn, tlen, ek, evl, val0, cap);
+        continue;
+      }
+      const int nb = (qn + 63) >> 6;
+      const Seq q{qp + q0, qn, 0};
+      if (20ll * nb * tn + 8ll * tn < (long long)FS_LEAF_BYTES) {
+        // a leaf: the whole matrix, then the walk from the corner
+        nleaf++;
+        c += (unsigned long long)qn * tn;
+        const Keep k{W.colP, W.colM, W.colS, nullptr, nullptr, nullptr};
+        (void)dp_pass(q, Seq{tp + t0, tn, 0}, 1, INT_MIN, s_row[wave], W.grow, k);
+        __threadfence();
+        // S(r, c) with the boundary row (c + 1) and column (r + 1)
+        auto score = [&](int r, int cc) -> int {
+          if (r < 0) return cc + 1;
+          if (cc < 0) return r + 1;
+          const size_t at = (size_t)(r >> 6) * (size_t)tn + (size_t)cc;
+          return row_score(W.colP[at], W.colM[at], W.colS[at], r, qn);
+        };
+        int r = qn - 1, cc = tn - 1, nops = 0;
+        int cur = best;
+        while (r >= 0 && cc >= 0) {
+          const int u = score(r - 1, cc), l = score(r, cc - 1), ul = score(r - 1, cc - 1);
+          int op;
+          if (u + 1 == cur) { op = OP_INSERT; r--; cur = u; }
+          else if (l + 1 == cur) { op = OP_DELETE; cc--; cur = l; }
+          else { op = ul == cur ? OP_MATCH : OP_MISMATCH; r--; cc--; cur = ul; }
+          if (lane == 0) W.ops[nops] = (uint8_t)op;
+          nops++;
+        }
+        // at a boundary the rest is flushed: the rows left are INSERTs, the columns DELETEs
+        const int up = r + 1, left = cc + 1;
+        for (int i = lane; i < up + left; i += 64)
+          W.ops[nops + i] = (uint8_t)(up ? OP_INSERT : OP_DELETE);
+        nops += up + left;
+        __threadfence();
+        const uint8_t *ops = W.ops;
+        emit_tags(S, nops, [ops, nops](int i) { return (int)ops[nops - 1 - i]; }, qp, qlen, tbgn,
+                  tlen, ek, evl, val0, cap);
+        __threadfence();                          // the buffer is reused by the next leaf
+        continue;
+      }
+      // a split (obtainAlignmentHirschberg): the last column of the left half and of the
+      // reversed right half, then the first row where the two meet at `best`
+      nsplit++;
+      c += (unsigned long long)qn * tn;
+      const int lw = tn / 2, rw = tn - lw;
+      const Keep kl{nullptr, nullptr, nullptr, W.endP, W.endM, W.endS};
+      const Keep kr{nullptr, nullptr, nullptr, W.endP + max_blocks, W.endM + max_blocks,
+                    W.endS + max_blocks};
+      (void)dp_pass(q, Seq{tp + t0, lw, 0}, 1, INT_MIN, s_row[wave], W.grow, kl);
+      (void)dp_pass(Seq{qp + q0, qn, 1}, Seq{tp + t0 + lw, rw, 1}, 1, INT_MIN, s_row[wave], W.grow, kr);
+      __threadfence();
+      // L[r] = ED(q[0..r], left), R[r] = ED(q[r..], right) = the reversed pass at row qn-1-r
+      auto Lrow = [&](int r) {
+        return row_score(W.endP[r >> 6], W.endM[r >> 6], W.endS[r >> 6], r, qn);
+      };
+      auto Rrow = [&](int r) {
+        const int x = qn - 1 - r;
+        return row_score(W.endP[max_blocks + (x >> 6)], W.endM[max_blocks + (x >> 6)],
+                         W.endS[max_blocks + (x >> 6)], x, qn);
+      };
+      int split = INT_MIN, ls = 0, rs = 0;
+      for (int r0 = 0; r0 <= qn - 2 && split == INT_MIN; r0 += 64) {
+        const int r = r0 + lane;
+        int a = 0, b = 0;
+        bool hit = false;
+        if (r <= qn - 2) { a = Lrow(r); b = Rrow(r + 1); hit = a + b == best; }
+        const uint64_t hm = __ballot(hit);
+        if (hm) {
+          const int first = __ffsll((unsigned long long)hm) - 1;
+          split = r0 + first;
+          ls = __shfl(a, first);
+          rs = __shfl(b, first);
+        }
+      }
+      if (split == INT_MIN) {
+        const int r_top = uni(Rrow(0)), l_bot = uni(Lrow(qn - 1));
+        if (lw + r_top == best) { split = -1; ls = lw; rs = r_top; }
+        else if (l_bot + rw == best) { split = qn - 1; ls = l_bot; rs = rw; }
+        else { split = qn - 1; ls = l_bot; rs = rw; }   // cannot happen: `best` is the distance
+      }
+      split = uni(split); ls = uni(ls); rs = uni(rs);
+      if (sp + 2 <= STACK_DEPTH) {
+        if (lane == 0) {
+          stack[sp][0] = q0 + split + 1; stack[sp][1] = qn - (split + 1);
+          stack[sp][2] = t0 + lw; stack[sp][3] = rw; stack[sp][4] = rs;
+          stack[sp + 1][0] = q0; stack[sp + 1][1] = split + 1;
+          stack[sp + 1][2] = t0; stack[sp + 1][3] = lw; stack[sp + 1][4] = ls;
+        }
+        sp += 2;
+      }
+      __builtin_amdgcn_wave_barrier();
+      __threadfence_block();
+    }
+    if (lane == 0) {
+      ntags_out[e] = S.ntags;
+      cells[e] += c;
+      nleaf_out[e] = nleaf;
+      nsplit_out[e] = nsplit;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ consensus
+
+__device__ __forceinline__ long long wave_max(long long v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long w = __shfl_xor(v, o);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(64)
+void k_fs_consensus(const Tp *__restrict__ tps, const uint32_t n_tp,
+                    const uint64_t *__restrict__ skeys, const uint32_t *__restrict__ svals,
+                    uint32_t *__restrict__ cov_all, uint32_t *__restrict__ lpos_all,
+                    int *__restrict__ lpidx_all, uint64_t *__restrict__ ckey_all,
+                    uint32_t *__restrict__ cfl_all, int *__restrict__ cscore_all,
+                    int *__restrict__ cback_all, uint32_t *__restrict__ clink_all,
+                    uint8_t *__restrict__ out_all, uint32_t *__restrict__ out_len,
+                    const uint32_t min_cov) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t lt = (1ull << lane) - 1;
+  for (uint32_t t = blockIdx.x; t < n_tp; t += gridDim.x) {
+    const Tp tp = tps[t];
+    const uint64_t *K = skeys + tp.tag_off;
+    const uint32_t *V = svals + tp.tag_off;
+    uint32_t *cov = cov_all + tp.cov_off;
+    uint32_t *lpos = lpos_all + tp.tag_off;
+    int *lpidx = lpidx_all + tp.tag_off;
+    uint64_t *ckey = ckey_all + tp.tag_off;
+    uint32_t *cfl = cfl_all + tp.tag_off;
+    int *cscore = cscore_all + tp.tag_off;
+    int *cback = cback_all + tp.tag_off;
+    uint32_t *clink = clink_all + tp.tag_off;
+    const uint32_t cap = tp.tag_cap;
+
+    // links: the runs of equal keys; coverage: the tags with delta 0
+    uint32_t nl = 0, nvalid = 0;
+    for (uint32_t i0 = 0; i0 < cap; i0 += 64) {
+      const uint32_t i = i0 + lane;
+      const uint64_t k = i < cap ? K[i] : KEY_NONE;
+      const bool valid = k != KEY_NONE;
+      const bool head = valid && (i == 0 || K[i - 1] != k);
+      if (valid && ((k >> 27) & 0xffff) == 0) atomicAdd(&cov[k >> 43], 1u);
+      const uint64_t hm = __ballot(head);
+      if (head) lpos[nl + __popcll(hm & lt)] = i;
+      nl += (uint32_t)__popcll(hm);
+      const uint64_t vm = __ballot(valid);
+      nvalid += (uint32_t)__popcll(vm);
+      if (vm != ~0ull) break;                     // sorted: the unused slots are last
+    }
+    nl = (uint32_t)uni((int)nl);
+    nvalid = (uint32_t)uni((int)nvalid);
+    __threadfence();
+    // columns: the runs of links with equal (t_pos, delta, slot)
+    uint32_t nc = 0;
+    for (uint32_t l0 = 0; l0 < nl; l0 += 64) {
+      const uint32_t li = l0 + lane;
+      const bool in = li < nl;
+      const uint64_t ck = in ? K[lpos[li]] >> KEY_COL_SHIFT : 0;
+      const bool head = in && (li == 0 || (K[lpos[li - 1]] >> KEY_COL_SHIFT) != ck);
+      const uint64_t hm = __ballot(head);
+      if (head) {
+        const uint32_t at = nc + (uint32_t)__popcll(hm & lt);
+        ckey[at] = ck;
+        cfl[at] = li;
+      }
+      nc += (uint32_t)__popcll(hm);
+    }
+    nc = (uint32_t)uni((int)nc);
+    __threadfence();
+    // the predecessor column of every link
+    for (uint32_t li = lane; li < nl; li += 64) {
+      const uint64_t k = K[lpos[li]];
+      const int prel = (int)((k >> 19) & 3);
+      int idx = -1;
+      if (prel) {
+        const uint64_t p_t = (k >> 43) - (prel == 1 ? 1 : 0);
+        const uint64_t p_ch = k & 7;
+        const uint64_t want = (p_t << 22) | (((k >> 3) & 0xffff) << 6) | ((p_ch < 4 ? p_ch : 4) << 3);
+        // ckey is key >> 21: t_pos at bit 22, delta at 6, slot at 3, the low three bits 0
+        uint32_t lo = 0, hi = nc;
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if ((ckey[mid] >> 3 << 3) < want) lo = mid + 1; else hi = mid;
+        }
+        if (lo < nc && (ckey[lo] >> 3 << 3) == want) idx = (int)lo;
+      }
+      lpidx[li] = idx;
+    }
+    __threadfence();
+    // the scan, in (t_pos, delta, slot) order.  ring: lane (x & 63) holds the score of column
+    // x for the last 64 columns; an older one is read back from memory.
+    int ring = 0;
+    int gbest = 0, gcol = -1;
+    for (uint32_t c = 0; c < nc; c++) {
+      const uint32_t l0 = cfl[c], l1 = c + 1 < nc ? cfl[c + 1] : nl;
+      const int covv = (int)cov[ckey[c] >> 22];
+      long long bestv = 0;
+      int bli = -1, bpidx = -1;
+      for (uint32_t lb = l0; lb < l1; lb += 64) {
+        const uint32_t li = lb + lane;
+        const bool in = li < l1;
+        int pidx = -1, cnt = 0;
+        uint32_t first = 0;
+        if (in) {
+          const uint32_t p = lpos[li];
+          cnt = (int)((li + 1 < nl ? lpos[li + 1] : nvalid) - p);
+          pidx = lpidx[li];
+          first = V[p];
+        }
+        const bool far = pidx >= 0 && c - (uint32_t)pidx > 64;
+        if (__any(far)) __threadfence();              // lane 0's stores, for every lane
+        const int near = __shfl(ring, pidx & 63);     // every lane is in: a ring lane may be idle
+        int s = 2 * cnt - covv;
+        if (pidx >= 0) s += far ? cscore[pidx] : near;
+        // a higher score wins; at equal scores the link that appeared first
+        const long long v = in && s > 0 ? ((long long)s << 32) | (long long)(0xffffffffu - first) : 0;
+        const long long mx = wave_max(v);
+        if (mx > bestv) {
+          bestv = mx;
+          const uint64_t who = __ballot(v == mx);
+          const int src = __ffsll((unsigned long long)who) - 1;
+          bli = __shfl((int)li, src);
+          bpidx = __shfl(pidx, src);
+        }
+      }
+      const int cs = (int)(bestv >> 32);
+      if (lane == 0) {
+        cscore[c] = cs;
+        cback[c] = cs > 0 ? bpidx : -1;
+        clink[c] = (uint32_t)bli;
+      }
+      if (lane == (int)(c & 63)) ring = cs;
+      if (cs > gbest) { gbest = cs; gcol = (int)c; }
+    }
+    __threadfence();
+    // the walk back.  The first letter is chosen by the index of the best link among the
+    // column's links in order of first appearance (g_best_ck, falconConsensus.C:232-236).
+    uint32_t index = 0;
+    uint8_t *out = out_all + tp.out_off;
+    const uint32_t ocap = 2u * (uint32_t)tp.len;
+    if (gcol >= 0) {
+      const uint32_t l0 = cfl[gcol], l1 = (uint32_t)gcol + 1 < nc ? cfl[gcol + 1] : nl;
+      const uint32_t bfirst = V[lpos[clink[gcol]]];
+      uint32_t rank = 0;
+      for (uint32_t lb = l0; lb < l1; lb += 64) {
+        const uint32_t li = lb + lane;
+        const bool before = li < l1 ? V[lpos[li]] < bfirst : false;
+        rank += (uint32_t)__popcll(__ballot(before));
+      }
+      int ck = rank < 4 ? (int)rank : 4;
+      int col = gcol;
+      while (true) {
+        const uint32_t pos = (uint32_t)(ckey[col] >> 22);
+        const bool low = cov[pos] <= min_cov;
+        const uint8_t bb = ck == 4 ? 0 : (uint8_t)((low ? "acgt" : "ACGT")[ck]);
+        const int prev = cback[col];
+        if (prev < 0 || index >= ocap) break;
+        col = prev;
+        ck = (int)((ckey[col] >> 3) & 7);
+        if (bb) {
+          if (lane == 0) out[ocap - 1 - index] = bb;
+          index++;
+        }
+      }
+    }
+    if (lane == 0) out_len[t] = index;
+  }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ host
+
+struct fs_ctx {
+  int device = 0;
+  fs_params P{};
+  hipStream_t stream = nullptr;
+  uint32_t first_iid = 0, nreads = 0;
+  std::vector<uint32_t> len;
+  std::vector<uint64_t> off;
+  uint8_t *d_fwd = nullptr, *d_rc = nullptr;
+  // the last result
+  bool have = false;
+  std::vector<uint32_t> tig_ids;
+  std::vector<uint64_t> r_off;
+  std::vector<uint8_t> r_bases;
+  std::vector<uint32_t> r_counts;
+  fs_stats S{};
+};
+
+namespace {
+
+int check_params(const fs_params *p) {
+  if (!p) return fail(FS_ERR_BAD_PARAM, "null parameters");
+  if (!(p->min_identity >= 0.0) || p->min_identity > 1.0)
+    return fail(FS_ERR_BAD_PARAM, "min_identity %g outside [0, 1]", p->min_identity);
+  return FS_OK;
+}
+
+void free_reads(fs_ctx *c) {
+  if (c->d_fwd) (void)hipFree(c->d_fwd);
+  if (c->d_rc) (void)hipFree(c->d_rc);
+  c->d_fwd = c->d_rc = nullptr;
+  c->nreads = 0;
+  c->len.clear();
+  c->off.clear();
+}
+
+template <class T> struct DevBuf {
+  T *p = nullptr;
+  size_t bytes = 0;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) {
+    bytes = std::max<size_t>(n, 1) * sizeof(T);
+    return hipMalloc((void **)&p, bytes);
+  }
+};
+
+// One batch of layouts on the device.
+int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &evs,
+              const std::vector<uint32_t> &ev_layout, const uint32_t layout0, uint32_t max_q,
+              uint32_t max_window, uint64_t total_tags, uint64_t total_cov, uint64_t total_out) {
+  std::vector<Tp> tps = tps_in;
+  const uint32_t n_tp = (uint32_t)tps.size(), n_ev = (uint32_t)evs.size();
+  fs_stats &S = c->S;
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, c->device));
+  const uint32_t want_waves = (uint32_t)prop.multiProcessorCount * 4;
+  const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_ev + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
+                                                                   want_waves / WAVES_PER_BLOCK));
+  const uint64_t waves = (uint64_t)blocks * WAVES_PER_BLOCK;
+  const uint32_t max_blocks = (max_q + 63) / 64 + 1;
+  const uint64_t ops_bytes = ((uint64_t)max_q + max_window + 64 + 15) & ~15ull;
+  const uint64_t grow_words = max_window > (uint32_t)LDS_COLUMNS ? ((uint64_t)max_window + 15) / 16 : 0;
+
+  DevBuf<Tp> d_tp;
+  DevBuf<Ev> d_ev;
+  DevBuf<Loc> d_loc;
+  DevBuf<unsigned long long> d_cells;
+  DevBuf<uint32_t> d_ntags, d_nleaf, d_nsplit, d_grow, d_vals, d_vals2, d_cov, d_lpos, d_cfl, d_clink,
+      d_outlen;
+  DevBuf<uint64_t> d_keys, d_keys2, d_colP, d_colM, d_endP, d_endM, d_ckey;
+  DevBuf<int> d_colS, d_endS, d_lpidx, d_cscore, d_cback, d_segoff;
+  DevBuf<uint8_t> d_ops, d_out, d_sort;
+  HIP_TRY(d_tp.alloc(n_tp));
+  HIP_TRY(d_ev.alloc(n_ev));
+  HIP_TRY(d_loc.alloc(n_ev));
+  HIP_TRY(d_cells.alloc(n_ev));
+  HIP_TRY(d_ntags.alloc(n_ev));
+  HIP_TRY(d_nleaf.alloc(n_ev));
+  HIP_TRY(d_nsplit.alloc(n_ev));
+  HIP_TRY(d_grow.alloc(grow_words * waves));
+  HIP_TRY(d_keys.alloc(total_tags));
+  HIP_TRY(d_keys2.alloc(total_tags));
+  HIP_TRY(d_vals.alloc(total_tags));
+  HIP_TRY(d_vals2.alloc(total_tags));
+  HIP_TRY(d_colP.alloc((uint64_t)LEAF_ENTRIES * waves));
+  HIP_TRY(d_colM.alloc((uint64_t)LEAF_ENTRIES * waves));
+  HIP_TRY(d_colS.alloc((uint64_t)LEAF_ENTRIES * waves));
+  HIP_TRY(d_endP.alloc(2ull * max_blocks * waves));
+  HIP_TRY(d_endM.alloc(2ull * max_blocks * waves));
+  HIP_TRY(d_endS.alloc(2ull * max_blocks * waves));
+  HIP_TRY(d_ops.alloc(ops_bytes * waves));
+  HIP_TRY(d_cov.alloc(total_cov));
+  HIP_TRY(d_lpos.alloc(total_tags));
+  HIP_TRY(d_lpidx.alloc(total_tags));
+  HIP_TRY(d_ckey.alloc(total_tags));
+  HIP_TRY(d_cfl.alloc(total_tags));
+  HIP_TRY(d_cscore.alloc(total_tags));
+  HIP_TRY(d_cback.alloc(total_tags));
+  HIP_TRY(d_clink.alloc(total_tags));
+  HIP_TRY(d_out.alloc(total_out));
+  HIP_TRY(d_outlen.alloc(n_tp));
+  HIP_TRY(d_segoff.alloc(n_tp + 1));
+  uint64_t scratch = 0;
+  for (size_t b : {d_keys.bytes, d_keys2.bytes, d_vals.bytes, d_vals2.bytes, d_colP.bytes, d_colM.bytes,
+                   d_colS.bytes, d_endP.bytes, d_endM.bytes, d_endS.bytes, d_ops.bytes, d_cov.bytes,
+                   d_lpos.bytes, d_lpidx.bytes, d_ckey.bytes, d_cfl.bytes, d_cscore.bytes,
+                   d_cback.bytes, d_clink.bytes, d_out.bytes, d_grow.bytes})
+    scratch += b;
+  S.scratch_bytes = std::max<uint64_t>(S.scratch_bytes, scratch);
+
+  std::vector<int> segoff(n_tp + 1);
+  for (uint32_t i = 0; i < n_tp; i++) segoff[i] = (int)tps[i].tag_off;
+  segoff[n_tp] = (int)total_tags;
+  hipStream_t s = c->stream;
+  HIP_TRY(hipMemcpyAsync(d_tp.p, tps.data(), n_tp * sizeof(Tp), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_ev.p, evs.data(), n_ev * sizeof(Ev), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(d_segoff.p, segoff.data(), (n_tp + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemsetAsync(d_keys.p, 0xff, std::max<uint64_t>(total_tags, 1) * 8, s));
+  HIP_TRY(hipMemsetAsync(d_vals.p, 0, std::max<uint64_t>(total_tags, 1) * 4, s));
+  HIP_TRY(hipMemsetAsync(d_cov.p, 0, std::max<uint64_t>(total_cov, 1) * 4, s));
+
+  hipEvent_t ev[5];
+  for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+  HIP_TRY(hipEventRecord(ev[0], s));
+  hipLaunchKernelGGL(k_fs_locate, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd, c->d_rc,
+                     d_ev.p, d_tp.p, n_ev, d_loc.p, d_cells.p, grow_words ? d_grow.p : nullptr,
+                     grow_words, 1.0 - c->P.min_identity);
+  hipError_t le = hipGetLastError();
+  HIP_TRY(hipEventRecord(ev[1], s));
+  if (le == hipSuccess) {
+    hipLaunchKernelGGL(k_fs_path, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd, c->d_rc,
+                       d_ev.p, d_tp.p, n_ev, d_loc.p, d_keys.p, d_vals.p, d_ntags.p, d_cells.p,
+                       d_nleaf.p, d_nsplit.p, d_colP.p, d_colM.p, d_colS.p, d_endP.p, d_endM.p,
+                       d_endS.p, d_ops.p, d_grow.p, max_blocks, ops_bytes, grow_words);
+    le = hipGetLastError();
+  }
+  HIP_TRY(hipEventRecord(ev[2], s));
+  if (le == hipSuccess && total_tags) {
+    size_t tb = 0;
+    le = hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, tb, d_keys.p, d_keys2.p, d_vals.p,
+                                                     d_vals2.p, (int)total_tags, (int)n_tp,
+                                                     d_segoff.p, d_segoff.p + 1, 0, 64, s);
+    if (le == hipSuccess) le = d_sort.alloc(tb);
+    if (le == hipSuccess)
+      le = hipcub::DeviceSegmentedRadixSort::SortPairs(d_sort.p, tb, d_keys.p, d_keys2.p, d_vals.p,
+                                                       d_vals2.p, (int)total_tags, (int)n_tp,
+                                                       d_segoff.p, d_segoff.p + 1, 0, 64, s);
+  }
+  HIP_TRY(hipEventRecord(ev[3], s));
+  if (le == hipSuccess) {
+    hipLaunchKernelGGL(k_fs_consensus, dim3(std::min<uint32_t>(n_tp, 65535u)), dim3(64), 0, s, d_tp.p,
+                       n_tp, d_keys2.p, d_vals2.p, d_cov.p, d_lpos.p, d_lpidx.p, d_ckey.p, d_cfl.p,
+                       d_cscore.p, d_cback.p, d_clink.p, d_out.p, d_outlen.p, c->P.min_coverage);
+    le = hipGetLastError();
+  }
+  HIP_TRY(hipEventRecord(ev[4], s));
+  hipError_t se = hipStreamSynchronize(s);
+  float ms[4] = {0, 0, 0, 0};
+  if (le == hipSuccess && se == hipSuccess)
+    for (int i = 0; i < 4; i++) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+  for (auto &x : ev) (void)hipEventDestroy(x);
+  HIP_TRY(le);
+  HIP_TRY(se);
+  S.ms_locate += ms[0];
+  S.ms_path += ms[1];
+  S.ms_sort += ms[2];
+  S.ms_consensus += ms[3];
+
+  std::vector<Loc> loc(n_ev);
+  std::vector<unsigned long long> cells(n_ev);
+  std::vector<uint32_t> ntags(n_ev), nleaf(n_ev), nsplit(n_ev), outlen(n_tp);
+  std::vector<uint8_t> out(std::max<uint64_t>(total_out, 1));
+  HIP_TRY(hipMemcpy(loc.data(), d_loc.p, n_ev * sizeof(Loc), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(cells.data(), d_cells.p, n_ev * 8ull, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ntags.data(), d_ntags.p, n_ev * 4ull, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nleaf.data(), d_nleaf.p, n_ev * 4ull, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nsplit.data(), d_nsplit.p, n_ev * 4ull, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(outlen.data(), d_outlen.p, n_tp * 4ull, hipMemcpyDeviceToHost));
+  if (total_out) HIP_TRY(hipMemcpy(out.data(), d_out.p, total_out, hipMemcpyDeviceToHost));
+  for (uint32_t e = 0; e < n_ev; e++) {
+    if (ntags[e] > evs[e].tag_cap)
+      return fail(FS_ERR_HIP, "evidence %u wrote %u tags into %u slots", e, ntags[e], evs[e].tag_cap);
+    const uint32_t l = ev_layout[e];
+    if (loc[e].ok) { c->r_counts[3 * (size_t)l + 0]++; S.n_aligned++; }
+    else { c->r_counts[3 * (size_t)l + 2]++; S.n_rejected++; }
+    S.dp_cells += cells[e];
+    S.n_tags += ntags[e];
+    S.n_leaves += nleaf[e];
+    S.n_splits += nsplit[e];
+  }
+  for (uint32_t i = 0; i < n_tp; i++) {
+    const uint64_t cap = 2ull * (uint64_t)tps[i].len;
+    if (outlen[i] > cap) return fail(FS_ERR_HIP, "template %u: consensus of %u bases", i, outlen[i]);
+    const uint8_t *p = out.data() + tps[i].out_off + (cap - outlen[i]);
+    c->r_bases.insert(c->r_bases.end(), p, p + outlen[i]);
+    c->r_off[layout0 + i + 1] = c->r_bases.size();
+  }
+  S.n_batches++;
+  return FS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void fs_params_init(fs_params *p) {
+  if (!p) return;
+  p->min_coverage = 4;          // falconsense.C:218-220
+  p->min_identity = 0.5;
+  p->min_output_length = 500;
+  p->hbm_budget = 0;
+}
+
+const char *fs_last_error(void) { return g_err.c_str(); }
+int fs_abi_version(void) { return FS_ABI_VERSION; }
+
+int fs_ctx_create(const fs_params *p, int device, fs_ctx **out) {
+  if (!out) return fail(FS_ERR_BAD_PARAM, "null out");
+  *out = nullptr;
+  if (int rc = check_params(p)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(FS_ERR_NO_DEVICE, "no HIP device %d", device);
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+    return fail(FS_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
+                prop.gcnArchName);
+  HIP_TRY(hipSetDevice(device));
+  fs_ctx *c = new fs_ctx;
+  c->device = device;
+  c->P = *p;
+  hipError_t e = hipStreamCreate(&c->stream);
+  if (e != hipSuccess) {
+    delete c;
+    return fail(FS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
+  }
+  *out = c;
+  return FS_OK;
+}
+
+void fs_ctx_destroy(fs_ctx *c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  free_reads(c);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+
+int fs_set_params(fs_ctx *c, const fs_params *p) {
+  if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
+  if (int rc = check_params(p)) return rc;
+  c->P = *p;
+  return FS_OK;
+}
+
+int fs_load_reads_device(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *d_bases,
+                         const uint64_t *d_offsets, const uint32_t *h_lengths) {
+  if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
+  if (nreads && (!d_bases || !d_offsets || !h_lengths))
+    return fail(FS_ERR_BAD_PARAM, "null read buffers");
+  if ((uint64_t)first_iid + nreads > 0xffffffffull)
+    return fail(FS_ERR_BAD_PARAM, "read IDs beyond 32 bits");
+  HIP_TRY(hipSetDevice(c->device));
+  free_reads(c);
+  c->have = false;
+  std::vector<uint64_t> off(nreads);
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < nreads; i++) {
+    if (h_lengths[i] > MAX_READLEN)
+      return fail(FS_ERR_BAD_INPUT, "read %u is %u bases, beyond AS_MAX_READLEN", first_iid + i,
+                  h_lengths[i]);
+    off[i] = total;
+    total += h_lengths[i];
+  }
+  DevBuf<uint32_t> bad, d_len;
+  DevBuf<uint64_t> d_off;
+  HIP_TRY(bad.alloc(1));
+  HIP_TRY(d_len.alloc(nreads));
+  HIP_TRY(d_off.alloc(nreads));
+  HIP_TRY(hipMalloc((void **)&c->d_fwd, std::max<uint64_t>(total, 1)));
+  HIP_TRY(hipMalloc((void **)&c->d_rc, std::max<uint64_t>(total, 1)));
+  HIP_TRY(hipMemsetAsync(bad.p, 0, 4, c->stream));
+  uint32_t h_bad = 0;
+  if (nreads) {
+    HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
+    const uint32_t grid = std::min<uint32_t>(nreads, 4096);
+    hipLaunchKernelGGL(k_fs_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, d_off.p,
+                       d_len.p, nreads, c->d_fwd, c->d_rc, bad.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (h_bad) {
+    free_reads(c);
+    return fail(FS_ERR_BAD_INPUT, "a read holds a byte outside ACGTN");
+  }
+  c->first_iid = first_iid;
+  c->nreads = nreads;
+  c->len.assign(h_lengths, h_lengths + nreads);
+  c->off = off;
+  return FS_OK;
+}
+
+int fs_load_reads(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
+                  const uint64_t *offsets, const uint32_t *lengths) {
+  if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
+  if (nreads && (!bases || !offsets || !lengths))
+    return fail(FS_ERR_BAD_PARAM, "null read buffers");
+  HIP_TRY(hipSetDevice(c->device));
+  uint64_t bytes = 0;
+  for (uint32_t i = 0; i < nreads; i++) bytes = std::max(bytes, offsets[i] + lengths[i]);
+  DevBuf<uint8_t> d_b;
+  DevBuf<uint64_t> d_o;
+  HIP_TRY(d_b.alloc(bytes));
+  HIP_TRY(d_o.alloc(nreads));
+  if (bytes) HIP_TRY(hipMemcpy(d_b.p, bases, bytes, hipMemcpyHostToDevice));
+  if (nreads) HIP_TRY(hipMemcpy(d_o.p, offsets, nreads * 8ull, hipMemcpyHostToDevice));
+  return fs_load_reads_device(c, first_iid, nreads, d_b.p, d_o.p, lengths);
+}
+
+int fs_consensus(fs_ctx *c, const fs_layout *layouts, uint64_t n_layouts, const fs_child *children,
+                 uint64_t n_children) {
+  if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
+  if ((n_layouts && !layouts) || (n_children && !children))
+    return fail(FS_ERR_BAD_PARAM, "null layouts or children");
+  if (n_layouts > 0xfffffff0ull) return fail(FS_ERR_BAD_PARAM, "more than 2^32 layouts in one call");
+  HIP_TRY(hipSetDevice(c->device));
+  c->have = false;
+  c->S = fs_stats{};
+  auto loaded = [&](uint32_t id) { return id >= c->first_iid && id - c->first_iid < c->nreads; };
+  // the checks the reference leaves to its assertions
+  for (uint64_t i = 0; i < n_layouts; i++) {
+    const fs_layout &l = layouts[i];
+    if (!loaded(l.tig_id))
+      return fail(FS_ERR_BAD_INPUT, "layout %llu: template read %u is not loaded",
+                  (unsigned long long)i, l.tig_id);
+    if (l.n_children > FS_MAX_CHILDREN)
+      return fail(FS_ERR_BAD_INPUT, "layout %llu (read %u) has %u children, more than %d",
+                  (unsigned long long)i, l.tig_id, l.n_children, FS_MAX_CHILDREN);
+    if ((uint64_t)l.first_child + l.n_children > n_children)
+      return fail(FS_ERR_BAD_PARAM, "layout %llu: children %u..%llu of %llu", (unsigned long long)i,
+                  l.first_child, (unsigned long long)l.first_child + l.n_children,
+                  (unsigned long long)n_children);
+    for (uint32_t k = 0; k < l.n_children; k++) {
+      const fs_child &ch = children[l.first_child + k];
+      if (!loaded(ch.ident))
+        return fail(FS_ERR_BAD_INPUT, "layout %llu: child read %u is not loaded",
+                    (unsigned long long)i, ch.ident);
+      const uint32_t len = c->len[ch.ident - c->first_iid];
+      if (ch.askip < 0 || ch.bskip < 0 || (uint64_t)ch.askip + (uint64_t)ch.bskip > len)
+        return fail(FS_ERR_BAD_INPUT, "layout %llu: child %u skips %d + %d of %u bases",
+                    (unsigned long long)i, ch.ident, ch.askip, ch.bskip, len);
+      if (ch.max <= ch.min)
+        return fail(FS_ERR_BAD_INPUT, "layout %llu: child %u placed at %d..%d", (unsigned long long)i,
+                    ch.ident, ch.min, ch.max);
+    }
+  }
+  c->tig_ids.resize(n_layouts);
+  c->r_off.assign(n_layouts + 1, 0);
+  c->r_bases.clear();
+  c->r_counts.assign(3 * n_layouts, 0);
+  c->S.n_layouts = n_layouts;
+  const double max_difference = 1.0 - c->P.min_identity;
+  const uint64_t budget = c->P.hbm_budget ? c->P.hbm_budget : (4ull << 30);
+  // device bytes a tag slot costs: keys and values twice, and the seven per-link arrays
+  const uint64_t per_tag = 2 * 8 + 2 * 4 + 4 + 4 + 8 + 4 + 4 + 4 + 4;
+
+  uint64_t i = 0;
+  while (i < n_layouts) {
+    std::vector<Tp> tps;
+    std::vector<Ev> evs;
+    std::vector<uint32_t> ev_layout;
+    uint64_t tags = 0, cov = 0, out = 0;
+    uint32_t max_q = 1, max_window = 1;
+    const uint64_t first = i;
+    for (; i < n_layouts; i++) {
+      const fs_layout &l = layouts[i];
+      const uint32_t tr = l.tig_id - c->first_iid;
+      const int32_t tlen = (int32_t)c->len[tr];
+      std::vector<Ev> mine;
+      uint64_t my_tags = 0;
+      uint32_t skipped = 0;
+      for (uint32_t k = 0; k <= l.n_children; k++) {
+        Ev e{};
+        int32_t len, bgn, end;
+        if (k == 0) {                               // the template, placed on itself
+          e.seq = c->off[tr];
+          len = tlen; bgn = 0; end = tlen;
+        } else {
+          const fs_child &ch = children[l.first_child + k - 1];
+          const uint32_t r = ch.ident - c->first_iid;
+          e.rc = ch.reverse ? 1 : 0;
+          e.seq = c->off[r] + (uint32_t)ch.askip;
+          len = (int32_t)c->len[r] - ch.askip - ch.bskip;
+          bgn = ch.min; end = ch.max;
+        }
+        if (len > tlen) len = tlen;                 // falconConsensus-alignTag.C:130-134
+        if (len < FS_MIN_EVIDENCE) { skipped++; continue; }
+        e.qlen = len;
+        e.tol = (int32_t)ceil(std::min(len, tlen) * max_difference * 1.1);
+        const int32_t expansion = (int32_t)((1.4 * len - (end - bgn)) / 2);
+        if (expansion > 0) { bgn -= expansion; end += expansion; }
+        if (bgn < 0) bgn = 0;
+        if (end > tlen) end = tlen;
+        if (end <= bgn)
+          return fail(FS_ERR_BAD_INPUT, "layout %llu: an evidence read is placed outside its "
+                      "template", (unsigned long long)i);
+        e.wb = bgn; e.we = end;
+        e.tag_cap = (uint32_t)len + (uint32_t)(end - bgn);
+        e.tag_off = my_tags;
+        my_tags += e.tag_cap;
+        mine.push_back(e);
+      }
+      const uint64_t need = (tags + my_tags) * per_tag + (cov + (uint64_t)tlen) * 4 + out + 2ull * tlen;
+      if (!tps.empty() && (need > budget || tags + my_tags > 0x7fffffffull)) break;
+      if (my_tags > 0x7fffffffull)
+        return fail(FS_ERR_UNSUPPORTED, "layout %llu needs %llu tag slots, more than 2^31",
+                    (unsigned long long)i, (unsigned long long)my_tags);
+      Tp t{};
+      t.seq = c->off[tr];
+      t.tag_off = tags;
+      t.cov_off = cov;
+      t.out_off = out;
+      t.tag_cap = (uint32_t)my_tags;
+      t.len = tlen;
+      for (Ev &e : mine) {
+        e.tag_off += tags;
+        e.tmpl = (uint32_t)tps.size();
+        max_q = std::max<uint32_t>(max_q, (uint32_t)e.qlen);
+        max_window = std::max<uint32_t>(max_window, (uint32_t)(e.we - e.wb));
+        evs.push_back(e);
+        ev_layout.push_back((uint32_t)i);
+      }
+      tps.push_back(t);
+      tags += my_tags;
+      cov += (uint64_t)tlen;
+      out += 2ull * tlen;
+      c->tig_ids[i] = l.tig_id;
+      c->r_counts[3 * i + 1] = skipped;
+      c->S.n_skipped += skipped;
+      c->S.n_evidence += (uint64_t)l.n_children + 1;
+    }
+    if (int rc = run_batch(c, tps, evs, ev_layout, (uint32_t)first, max_q, max_window, tags, cov, out))
+      return rc;
+  }
+  c->have = true;
+  return FS_OK;
+}
+
+int fs_result_size(const fs_ctx *c, uint64_t *n_layouts, uint64_t *n_bases) {
+  if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
+  if (!c->have) return fail(FS_ERR_STATE, "no result: call fs_consensus first");
+  if (n_layouts) *n_layouts = c->tig_ids.size();
+  if (n_bases) *n_bases = c->r_bases.size();
+  return FS_OK;
+}
+
+int fs_fetch(const fs_ctx *c, uint8_t *bases, uint64_t *offsets, uint32_t *counts) {
+  if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
+  if (!c->have) return fail(FS_ERR_STATE, "no result: call fs_consensus first");
+  if (bases && !c->r_bases.empty()) memcpy(bases, c->r_bases.data(), c->r_bases.size());
+  if (offsets) memcpy(offsets, c->r_off.data(), c->r_off.size() * 8);
+  if (counts && !c->r_counts.empty()) memcpy(counts, c->r_counts.data(), c->r_counts.size() * 4);
+  return FS_OK;
+}
+
+int fs_write_fasta_file(const fs_ctx *c, FILE *f) {
+  if (!c || !f) return fail(FS_ERR_BAD_PARAM, "null argument");
+  if (!c->have) return fail(FS_ERR_STATE, "no result: call fs_consensus first");
+  std::string out;
+  for (size_t i = 0; i < c->tig_ids.size(); i++) {
+    out.clear();
+    fs_fasta_pieces(out, nullptr, c->tig_ids[i], c->r_bases.data() + c->r_off[i],
+                    c->r_off[i + 1] - c->r_off[i], c->P.min_output_length);
+    if (!out.empty() && fwrite(out.data(), 1, out.size(), f) != out.size())
+      return fail(FS_ERR_STATE, "short write");
+  }
+  return FS_OK;
+}
+
+int fs_write_fasta(const fs_ctx *c, const char *path) {
+  if (!c || !path) return fail(FS_ERR_BAD_PARAM, "null argument");
+  FILE *f = fopen(path, "wb");
+  if (!f) return fail(FS_ERR_BAD_PARAM, "cannot write %s", path);
+  const int rc = fs_write_fasta_file(c, f);
+  if (fclose(f) != 0 && rc == FS_OK) return fail(FS_ERR_STATE, "cannot close %s", path);
+  return rc;
+}
+
+int fs_get_stats(const fs_ctx *c, fs_stats *out) {
+  if (!c || !out) return fail(FS_ERR_BAD_PARAM, "null argument");
+  *out = c->S;
+  return FS_OK;
+}
+
+}  // extern "C"
