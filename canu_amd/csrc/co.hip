@@ -14,9 +14,10 @@
 // correctOverlaps' Prefix_Edit_Dist (correctOverlaps-Prefix_Edit_Distance.C:165-312) with
 // Compute_Delta on the path that reaches an end, the leading-gap trim, the failure tests and
 // the nine counters -- and leaves `errors` and `olapLen`; the host encodes the evalue.  The
-// aligner is k_fe_align's (fe.hip): lanes as diagonals, 32 bases per slide step, spans staged
-// in LDS, a register window with the row log in global memory behind it, a re-run with the
-// worst-case log for the alignments that outgrow the first.
+// aligner is ped_wave.h's, shared with k_fe_align: lanes as diagonals, 32 bases per slide step,
+// spans staged in LDS, a register window with the row log in global memory behind it, a re-run
+// with the worst-case log for the alignments that outgrow the first.  What is correctOverlaps'
+// own is the one-clause Max_Score test and that only an alignment to an end is traced back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +33,9 @@
 #include <vector>
 
 #include "../../include/canu_co.h"
+#include "hip_raii.h"
+#include "ped_host.h"
+#include "ped_wave.h"
 
 namespace {
 
@@ -55,11 +59,12 @@ int fail(int code, const char *fmt, ...) {
                   hipGetErrorString(e_));                                             \
   } while (0)
 
-constexpr uint32_t AS_MAX_READLEN = (1u << 21) - 1;
+using namespace ped;
+
+static_assert(CO_WINDOW_DIAGS == PED_WINDOW_DIAGS, "canu_co.h names the aligner's window");
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr uint64_t SCRATCH_BUDGET = 16ull << 30;      // row logs of one launch, bytes
 constexpr uint64_t CORRECT_BUDGET = 4ull << 30;       // per-block work areas of k_co_correct
-constexpr int PAD_WORDS = 3;                          // a 32-base window may start at the last base
 constexpr int AS_MAX_EVALUE = 4095;                   // ovOverlap.H:41-42
 // Vote_Value_t (correctionOutput.H:24-37)
 enum { V_IDENT = 0, V_DELETE = 1, V_A_SUBST = 2, V_T_SUBST = 5, V_A_INSERT = 6, V_T_INSERT = 9 };
@@ -70,7 +75,7 @@ enum : uint32_t { F_DONE = 1, F_TO_END = 2, F_OVERFLOW = 4, F_GENERIC = 8, F_INT
                   F_STAGED = 32 };
 // the nine counters, in the order Redo_Olaps prints them
 enum { C_FWD = 0, C_REV, C_TOTAL, C_BOTH, C_EITHER, C_END, C_LENGTH, C_RHA_FAIL, C_RHA_PASS, NCOUNT };
-constexpr int LDS_STRAND_WORDS = (CO_LDS_BASES + 15) / 16 + 4;
+constexpr int LDS_STRAND_WORDS = lds_strand_words(CO_LDS_BASES);
 
 struct Adjust { int32_t adjpos, adjust; };   // Adjust_t, correctOverlaps.H:107-110
 
@@ -125,91 +130,7 @@ __global__ void k_co_encode(const uint8_t *__restrict__ bases, const uint64_t *_
   }
 }
 
-// ------------------------------------------------------------------ wave helpers (fe.hip's)
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ int from_lower(int v) {   // lane l <- v[(l - 1) & 63]
-  return __builtin_amdgcn_update_dpp(0, v, 0x13C, 0xf, 0xf, false);
-}
-__device__ __forceinline__ int from_upper(int v) {   // lane l <- v[(l + 1) & 63]
-  return __builtin_amdgcn_update_dpp(0, v, 0x134, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-  const int NEG = (int)0x80000000;
-  int t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x111, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x112, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x114, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x118, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x142, 0xa, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x143, 0xc, 0xf, false); v = v > t ? v : t;
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
-// bit k of the result is bit ((k + s) & 63) of mask: lanes in diagonal order from `left`
-__device__ __forceinline__ uint64_t rot_to(uint64_t mask, int left) {
-  const int s = left & 63;
-  return s ? (mask >> s) | (mask << (64 - s)) : mask;
-}
-
-__device__ __forceinline__ void wave_fence() { __threadfence_block(); }
-
-__device__ __forceinline__ uint64_t fetch32(const uint32_t *P, int pos) {
-  const uint32_t *w = P + (pos >> 4);
-  const int s = (pos & 15) * 2;
-  const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-  uint64_t x = lo >> s;
-  if (s) x |= (uint64_t)w[2] << (64 - s);
-  return x;
-}
-
-__device__ __forceinline__ int code_at(const uint32_t *P, int pos) {
-  return (P[pos >> 4] >> ((pos & 15) * 2)) & 3;
-}
-
-// The inner while of Prefix_Edit_Dist (:227-228) from (row, row + d).
-__device__ __forceinline__ int slide(const uint32_t *A, int ab, const uint32_t *B, int bb, int row,
-                                     int d, int m, int n) {
-  const int rem = min(m - row, n - (row + d));
-  int adv = 0;
-  while (adv < rem) {
-    const uint64_t x = fetch32(A, ab + row + adv) ^ fetch32(B, bb + row + d + adv);
-    if (x) {
-      adv += __builtin_ctzll(x) >> 1;
-      break;
-    }
-    adv += 32;
-  }
-  return row + min(adv, rem);
-}
-
-struct RowMeta { int off, lo, hi; };   // value of (e, d) at log[off + d] for lo <= d <= hi, else -2
-
-__device__ __forceinline__ int row_get(const int32_t *log, const RowMeta M, int d) {
-  return (d >= M.lo && d <= M.hi) ? log[M.off + d] : -2;
-}
-
 // ------------------------------------------------------------------ the corrections
-
-__device__ __forceinline__ int block_scan_incl(int v, int *lds, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int s = 1; s < 64; s <<= 1) {
-    const int t = __shfl_up(v, s);
-    if (lane >= s) v += t;
-  }
-  __syncthreads();
-  if (lane == 63) lds[w] = v;
-  __syncthreads();
-  int add = 0, tot = 0;
-  for (int k = 0; k < (int)(blockDim.x >> 6); k++) {
-    if (k < w) add += lds[k];
-    tot += lds[k];
-  }
-  total = tot;
-  return v + add;
-}
 
 struct CorrectArgs {
   const uint32_t *ofwd;              // the reads as loaded, packed
@@ -377,14 +298,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 8) void k_co_align(const Alig
   int32_t *const delta = stk + (X.max_limit + 4);
 
   for (;;) {
-    uint32_t slot = 0;
-    if (lane == 0) slot = atomicAdd(X.next, 1u);
-    slot = (uint32_t)uni((int)slot);
+    const uint32_t slot = next_job(X.next, lane);
     if (slot >= X.njobs) break;
     const uint32_t oi = X.order[slot];
     const Job J = X.jobs[oi];
-    uint32_t flags = 0, nrows = 0;
-
     // :375-404, the adjusted hangs
     int ab = 0, bb = 0;
     if (J.a_hang > 0)
@@ -400,221 +317,32 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 8) void k_co_align(const Alig
       if (lane == 0) { X.flags[oi] = F_INTERNAL; X.rows[oi] = 0; }
       continue;
     }
-    const int shorter = min(m, n);
-    // the two spans the aligner reads: in LDS where both fit, else where they lie
+    // the two spans the aligner reads
     const uint32_t *As = X.fwd + J.a_word, *B = (J.b_rc ? X.rc : X.fwd) + J.b_word;
     int as = ab;
-    // A row never passes min(m, n - d) and |d| <= limit: what lies beyond is never read
-    const int ma = min(m, n + J.limit), nb = min(n, m + J.limit);
-    if (max(ma, nb) <= CO_LDS_BASES) {
-      uint32_t *const la = s_strand[threadIdx.x >> 6][0], *const lb = s_strand[threadIdx.x >> 6][1];
-      const int wa = ((as & 15) + ma) / 16 + PAD_WORDS, wb = ((bb & 15) + nb) / 16 + PAD_WORDS;
-      for (int i = lane; i < wa; i += 64) la[i] = As[(as >> 4) + i];
-      for (int i = lane; i < wb; i += 64) lb[i] = B[(bb >> 4) + i];
-      wave_fence();
-      As = la; as &= 15;
-      B = lb; bb &= 15;
+    uint32_t flags = 0;
+    if (ped_stage<CO_LDS_BASES>(As, as, B, bb, m, n, J.limit, s_strand[threadIdx.x >> 6][0],
+                                s_strand[threadIdx.x >> 6][1], lane))
       flags |= F_STAGED;
-    }
 
-    int errors = 0, a_end = 0, b_end = 0, delta_len = 0;
-    bool to_end = false, aborted = false;
-
-    const int row0 = uni(slide(As, as, B, bb, 0, 0, m, n));
-    if (row0 == shorter) {                                     // :196-201
-      a_end = b_end = row0;
-      to_end = true;
-    } else {
-      if (lane == 0) { log[0] = row0; meta[0] = 0; meta[1] = 0; meta[2] = 0; }
-      RowMeta PM{0, 0, 0};                                     // the row before
-      uint64_t logpos = 1;
-      int left = 0, right = 0;
-      int best_d = 0, longest = 0;
-      double max_score = 0.0;
-      int ms_len = 0, ms_d = 0;
-      int pv = lane == 0 ? row0 : -2;                          // row e-1 at this lane's diagonal
-      bool pv_valid = true;
-      int end_e = 0, end_d = 0, end_row = 0;
-      bool ended = false;
-
-      for (int e = 1; e <= J.limit; e++) {
-        left = max(left - 1, -e);
-        right = min(right + 1, e);
-        const int width = right - left + 1;
-        if (logpos + (uint64_t)width > X.log_cap) { aborted = true; break; }
-        const int off = (int)logpos - left;
-        const int lim = X.match_limit[e];
-        nrows++;
-        wave_fence();                                          // row e-1 and its meta are written
-        int new_left, new_right, row_max = 0, row_max_d = 0;
-        bool hit = false;
-        int hit_d = 0, hit_row = 0;
-
-        if (width <= CO_WINDOW_DIAGS) {
-          const int d = left + ((lane - left) & 63);
-          const bool active = d <= right;
-          if (!pv_valid) pv = row_get(log, PM, d);
-          const int lo_n = from_lower(pv), up_n = from_upper(pv);
-          int row = max(max(1 + pv, lo_n), up_n + 1);
-          if (active) {
-            row = slide(As, as, B, bb, row, d, m, n);
-            log[off + d] = row;
-          } else {
-            row = -2;
-          }
-          const uint64_t em = rot_to(__ballot(active && (row == m || row + d == n)), left);
-          if (em) {
-            hit = true;
-            hit_d = left + __builtin_ctzll(em);
-            hit_row = __builtin_amdgcn_readlane(row, hit_d & 63);
-          } else {
-            const bool keep = active && ((d < 0 ? row : row + d) >= lim);   // :257-275
-            const uint64_t km = rot_to(__ballot(keep), left);
-            if (km == 0) {
-              new_left = right + 1;
-              new_right = right;
-            } else {
-              new_left = left + __builtin_ctzll(km);
-              new_right = left + 63 - __builtin_clzll(km);
-              const bool in = active && d >= new_left && d <= new_right;
-              row_max = wave_max(in ? row : -2);
-              row_max_d = left + __builtin_ctzll(rot_to(__ballot(in && row == row_max), left));
-              pv = in ? row : -2;
-              pv_valid = true;
-            }
-          }
-        } else {
-          flags |= F_GENERIC;
-          pv_valid = false;
-          const int nchunk = (width + 63) >> 6;
-          // One pass: the pruning (:257-275) and the leftmost maximum of the pruned band
-          // (:279-284) are kept from the ballots of the computing pass.  `com` is the maximum
-          // over [new_left, new_right] so far, `pen` over what lies right of new_right and
-          // joins the band only if a later diagonal holds the limit.
-          new_left = right + 1;
-          new_right = right;
-          bool any = false;
-          int com_max = -2, com_d = 0, pen_max = -2, pen_d = 0;
-          for (int c = 0; c < nchunk && !hit; c++) {
-            const int base = left + c * 64;
-            const int d = base + lane;
-            const bool active = d <= right;
-            int row = -2;
-            if (active) {
-              row = max(max(1 + row_get(log, PM, d), row_get(log, PM, d - 1)),
-                        row_get(log, PM, d + 1) + 1);
-              row = slide(As, as, B, bb, row, d, m, n);
-              log[off + d] = row;
-            }
-            const uint64_t em = __ballot(active && (row == m || row + d == n));
-            if (em) {
-              hit = true;
-              const int l = __builtin_ctzll(em);
-              hit_d = base + l;
-              hit_row = __builtin_amdgcn_readlane(row, l);
-              break;
-            }
-            const uint64_t km = __ballot(active && ((d < 0 ? row : row + d) >= lim));
-            if (km) {
-              const int fk = __builtin_ctzll(km), lk = 63 - __builtin_clzll(km);
-              const bool in1 = active && lane >= (any ? 0 : fk) && lane <= lk;
-              const int mx1 = wave_max(in1 ? row : -2);
-              const int d1 = base + __builtin_ctzll(__ballot(in1 && row == mx1));
-              if (pen_max > com_max) { com_max = pen_max; com_d = pen_d; }   // strictly: leftmost
-              if (mx1 > com_max) { com_max = mx1; com_d = d1; }
-              if (!any) new_left = base + fk;
-              any = true;
-              new_right = base + lk;
-              const bool in2 = active && lane > lk;
-              pen_max = -2;
-              if (__ballot(in2)) {
-                pen_max = wave_max(in2 ? row : -2);
-                pen_d = base + __builtin_ctzll(__ballot(in2 && row == pen_max));
-              }
-            } else if (any) {
-              const int mx = wave_max(active ? row : -2);
-              if (mx > pen_max) {
-                pen_max = mx;
-                pen_d = base + __builtin_ctzll(__ballot(active && row == mx));
-              }
-            }
-          }
-          row_max = com_max;
-          row_max_d = com_d;
-        }
-
-        if (hit) {                                             // :236-254
-          if (hit_row == m && 1 + row_get(log, PM, hit_d + 1) == hit_row && hit_d < right)
-            hit_d++;                                           // the last error is a mismatch
-          ended = true;
-          end_e = e;
-          end_d = hit_d;
-          end_row = hit_row;
-          break;
-        }
-        left = new_left;
-        right = new_right;
-        if (lane == 0) { meta[3 * e] = off; meta[3 * e + 1] = left; meta[3 * e + 2] = right; }
-        PM = RowMeta{off, left, right};
-        logpos += (uint64_t)width;
-        if (left > right) break;
-        if (row_max > longest) {                               // :279-284
-          best_d = row_max_d;
-          longest = row_max;
-        }
-        const int score = (int)((double)longest * 0.272 - (double)e);   // :286, int32: truncated
-        if ((double)score > max_score) {                       // :292, the one test
-          max_score = (double)score;
-          ms_len = longest;
-          ms_d = best_d;
-        }
-      }
-
-      if (!aborted) {
-        if (!ended) {                                          // :303-311
-          errors = J.limit + 1; a_end = ms_len; b_end = ms_len + ms_d; to_end = false;
-        } else {
-          errors = end_e; a_end = end_row; b_end = end_row + end_d; to_end = true;
-          // Compute_Delta (:30-75); every lane walks the same path, lane 0 writes the stack
-          wave_fence();
-          int last = end_row, sl = 0, d = end_d;
-          for (int k = end_e; k > 0; k--) {
-            const RowMeta M{meta[3 * (k - 1)], meta[3 * (k - 1) + 1], meta[3 * (k - 1) + 2]};
-            int from = d;
-            int mx = 1 + row_get(log, M, d);
-            int j = row_get(log, M, d - 1);
-            if (j > mx) { from = d - 1; mx = j; }
-            j = 1 + row_get(log, M, d + 1);
-            if (j > mx) { from = d + 1; mx = j; }
-            if (from == d - 1) {
-              if (lane == 0) stk[sl] = mx - last - 1;
-              sl++;
-              d--;
-              last = row_get(log, M, from);
-            } else if (from == d + 1) {
-              if (lane == 0) stk[sl] = last - (mx - 1);
-              sl++;
-              d++;
-              last = row_get(log, M, from);
-            }
-          }
-          if (lane == 0) stk[sl] = last + 1;
-          sl++;
-          wave_fence();
-          delta_len = sl - 1;
-          for (int k = lane; k < delta_len; k += 64) {
-            const int i = sl - 1 - k;
-            const int v = stk[i], s = stk[i - 1];
-            delta[k] = abs(v) * ((s > 0) - (s < 0));
-          }
-          wave_fence();
-        }
-      }
-    }
-
-    if (aborted) {
-      if (lane == 0) { X.flags[oi] = F_OVERFLOW | flags; X.rows[oi] = nrows; }
+    const PedRows R = ped_rows(As, as, B, bb, m, n, J.limit, X.match_limit, log, meta, X.log_cap, lane,
+                               [](int score, double max_score, int, int, int) {
+                                 return (double)score > max_score;
+                               });
+    if (R.generic) flags |= F_GENERIC;
+    if (R.aborted) {
+      if (lane == 0) { X.flags[oi] = F_OVERFLOW | flags; X.rows[oi] = R.nrows; }
       continue;
+    }
+    // the alignment to the end and its delta, or else the Max_Score cell as where it stopped and
+    // one error too many (:303-311)
+    const bool to_end = R.ended;
+    int errors, a_end, b_end, delta_len = 0;
+    if (!to_end) {
+      errors = J.limit + 1; a_end = R.ms_len; b_end = R.ms_len + R.ms_d;
+    } else {
+      errors = R.end_e; a_end = R.end_row; b_end = R.end_row + R.end_d;
+      delta_len = ped_delta(log, meta, stk, delta, R.end_e, R.end_d, R.end_row, lane);
     }
 
     // :431-468: a leading run of gaps on the side that hangs, against the hang as stored
@@ -645,90 +373,10 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 8) void k_co_align(const Alig
       X.errors[oi] = errors;
       X.olap_len[oi] = olap_len;
       X.flags[oi] = flags | F_DONE;
-      X.rows[oi] = nrows;
+      X.rows[oi] = R.nrows;
     }
   }
 }
-
-// ------------------------------------------------------------------ Edit_Match_Limit
-
-// Binomial_Bound.C:47 and Initialize_Match_Limit (:116), as correctOverlaps.C:131-133 calls it.
-int binomial_bound(int e, double p, int start) {
-  const double bound = 1e-4, thold = 3.62;
-  const double q = 1.0 - p;
-  if (start < e) start = e;
-  for (int n = start; n < (int)AS_MAX_READLEN; n++) {
-    if (n <= 35) {
-      double sum = 0.0, p_pow = 1.0, q_pow = pow(q, n);
-      int bin = 1, ct = 0;
-      for (int k = 0; k < e && 1.0 - sum > bound; k++) {
-        const double x = bin * p_pow * q_pow;
-        sum += x;
-        bin *= n - ct;
-        bin /= ++ct;
-        p_pow *= p;
-        q_pow /= q;
-      }
-      if (1.0 - sum > bound) return n;
-    } else {
-      const double z = (e - 0.5 - n * p) / sqrt(n * p * q);
-      if (z <= thold) return n;
-      double sum = 0.0, mu_pow = 1.0, fact = 1.0;
-      const double pc = exp(-n * p);
-      for (int k = 0; k < e; k++) {
-        sum += mu_pow * pc / fact;
-        mu_pow *= n * p;
-        fact *= k + 1;
-      }
-      if (1.0 - sum > bound) return n;
-    }
-  }
-  return AS_MAX_READLEN;
-}
-
-void init_match_limit(std::vector<int32_t> &ml, double erate, int32_t max_errors, int32_t upto) {
-  ml.assign((size_t)upto + 1, 0);
-  int32_t e = 0, s = 1;
-  const int32_t l = std::min<int32_t>(max_errors, 2000);
-  while (e <= 1 && e <= upto) ml[e++] = 0;
-  while (e < l && e <= upto) {
-    s = binomial_bound(e - 1, erate, s);
-    ml[e] = s - 1;
-    e++;
-  }
-  if (e > upto) return;
-  const double sl = 0.982064188397525 / erate + 0.067835741959926;   // AS_MAX_READLEN_BITS 21
-  double vl = ml[e - 1] + sl;
-  while (e < max_errors && e <= upto) {
-    ml[e] = (int32_t)ceil(vl);
-    vl += sl;
-    e++;
-  }
-}
-
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { release(); }
-  void release() { if (p) (void)hipFree(p); p = nullptr; }
-  hipError_t alloc(size_t n) {
-    release();
-    return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
-  }
-};
-
-struct Event {               // a hipEvent_t that is destroyed on every way out
-  hipEvent_t e = nullptr;
-  Event() = default;
-  Event(const Event &) = delete;
-  Event &operator=(const Event &) = delete;
-  ~Event() { if (e) (void)hipEventDestroy(e); }
-  hipError_t create() { return hipEventCreate(&e); }
-  operator hipEvent_t() const { return e; }
-};
 
 int check_params(const co_params *p) {
   if (!p) return fail(CO_ERR_BAD_PARAM, "null parameters");
@@ -1129,8 +777,7 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
   if (const char *e = getenv("CANU_CO_LOG_PER_ERROR")) per_error = std::max(1, atoi(e));
   std::vector<uint32_t> todo = order, fl(n), rows(n);
   int32_t cur_limit = max_limit;
-  const uint64_t worst = ((uint64_t)max_limit + 1) * ((uint64_t)max_limit + 1) + 64;
-  uint64_t log_cap = std::min<uint64_t>((uint64_t)per_error * max_limit + 64, worst);
+  uint64_t log_cap = row_log_first(per_error, max_limit);
   // test knob: the exact size of the first row log
   if (const char *e = getenv("CANU_CO_LOG_CAP")) log_cap = std::max<uint64_t>(2, strtoull(e, nullptr, 10));
   Event e0, e1;
@@ -1145,7 +792,7 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
     const uint64_t fit = std::max<uint64_t>(1, SCRATCH_BUDGET / (per_wave * 4));
     const uint64_t nwaves = std::min<uint64_t>({nt, (uint64_t)c->n_cu * 8 * WAVES_PER_BLOCK, fit});
     const uint32_t blocks = (uint32_t)((nwaves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    if (log_cap > 0x7fff0000ull)
+    if (log_cap > ROW_LOG_MAX)
       return fail(CO_ERR_UNSUPPORTED, "a row log of %llu entries (%d errors allowed) is beyond "
                   "the 32-bit offsets of this build", (unsigned long long)log_cap, cur_limit);
     DevBuf<int32_t> d_scratch;
@@ -1186,11 +833,10 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
       }
     }
     if (!again.empty()) {
-      if (log_cap >= ((uint64_t)next_limit + 1) * ((uint64_t)next_limit + 1))
-        return fail(CO_ERR_HIP, "row log overflow at its worst-case size");
+      log_cap = row_log_regrown(log_cap, next_limit);
+      if (!log_cap) return fail(CO_ERR_HIP, "row log overflow at its worst-case size");
       c->S.regrows++;
       cur_limit = next_limit;
-      log_cap = ((uint64_t)next_limit + 1) * ((uint64_t)next_limit + 1) + 64;   // sum of 2e + 1
     }
     todo.swap(again);
   }

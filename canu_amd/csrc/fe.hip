@@ -6,14 +6,11 @@
 // (findErrors-Analyze_Alignment.C:100-293) -- so nothing goes back to the host per overlap.
 //
 // Reads are 2 bits per base (every byte outside ACGTacgt is 'a'), forward and reverse
-// complemented.  A row of the edit array lives with lanes as diagonals: lane (d & 63) holds
-// diagonal d, so the band may drift without moving registers, and the two neighbours come by
-// one DPP wave rotate each.  The slide compares 32 bases per step (xor of two 64-bit windows,
-// count of trailing zeros).  Spans of up to FE_LDS_BASES bases are staged in the wave's LDS
-// strands first; longer ones are fetched from global memory.  A row wider than FE_WINDOW_DIAGS is computed in chunks of 64 that
-// read the row before from the row log.  Every row goes to the wave's row log in global memory
-// (the traceback needs them all); only its pruned band is ever read again, and a read outside
-// that band is the reference's -2.
+// complemented.  The aligner is ped_wave.h's, shared with k_co_align: lanes as diagonals, a
+// register window of FE_WINDOW_DIAGS diagonals with the row log in global memory behind it.
+// Spans of up to FE_LDS_BASES bases are staged in the wave's LDS strands first; longer ones are
+// fetched from global memory.  What is findErrors' own is the second clause of the Max_Score
+// test and the traceback from the Max_Score cell when no row reaches an end.
 //
 // Tallies are 32-bit counters per base (44 bytes per base of the range): the nine point votes by
 // atomicAdd, `confirmed` and `no_insert` as difference pairs (+1 at the start of a run, -1 past
@@ -34,6 +31,9 @@
 #include <vector>
 
 #include "../../include/canu_fe.h"
+#include "hip_raii.h"
+#include "ped_host.h"
+#include "ped_wave.h"
 
 namespace {
 
@@ -57,10 +57,11 @@ int fail(int code, const char *fmt, ...) {
                   hipGetErrorString(e_));                                             \
   } while (0)
 
-constexpr uint32_t AS_MAX_READLEN = (1u << 21) - 1;
+using namespace ped;
+
+static_assert(FE_WINDOW_DIAGS == PED_WINDOW_DIAGS, "canu_fe.h names the aligner's window");
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr uint64_t SCRATCH_BUDGET = 16ull << 30;      // row logs of one launch, bytes
-constexpr int PAD_WORDS = 3;                          // a 32-base window may start at the last base
 constexpr int MAX_VOTE = 255, MAX_DEGREE = 32767;     // findErrors.H:87-90
 constexpr int MIN_HAPLO_OCCURS = 3;                   // findErrors.H:102
 constexpr int NPLANES = 11;
@@ -70,9 +71,7 @@ enum { PL_CONFIRMED = 0, PL_DELETES = 1, PL_SUBST = 2, PL_NO_INSERT = 6, PL_INSE
 // per-overlap outcome
 enum : uint32_t { F_PASSED = 1, F_FAILED = 2, F_OVERFLOW = 4, F_GENERIC = 8, F_INTERNAL = 16,
                   F_STAGED = 32 };
-// words of one LDS strand: a span keeps its bit offset in its first word (up to 15 bases) and
-// a 32-base window may start at its last base (PAD_WORDS)
-constexpr int LDS_STRAND_WORDS = (FE_LDS_BASES + 15) / 16 + 4;
+constexpr int LDS_STRAND_WORDS = lds_strand_words(FE_LDS_BASES);
 
 struct Job {                 // one overlap, as Process_Olap sets it up (:72-119)
   uint64_t a_word, b_word;   // first packed word of A (forward) and of B (as oriented)
@@ -128,72 +127,6 @@ __global__ void k_fe_encode(const uint8_t *__restrict__ bases, const uint64_t *_
   }
 }
 
-// ------------------------------------------------------------------ wave helpers
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ int from_lower(int v) {   // lane l <- v[(l - 1) & 63]
-  return __builtin_amdgcn_update_dpp(0, v, 0x13C, 0xf, 0xf, false);
-}
-__device__ __forceinline__ int from_upper(int v) {   // lane l <- v[(l + 1) & 63]
-  return __builtin_amdgcn_update_dpp(0, v, 0x134, 0xf, 0xf, false);
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-  const int NEG = (int)0x80000000;
-  int t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x111, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x112, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x114, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x118, 0xf, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x142, 0xa, 0xf, false); v = v > t ? v : t;
-  t = __builtin_amdgcn_update_dpp(NEG, v, 0x143, 0xc, 0xf, false); v = v > t ? v : t;
-  return __builtin_amdgcn_readlane(v, 63);
-}
-
-// bit k of the result is bit ((k + s) & 63) of mask: lanes in diagonal order from `left`
-__device__ __forceinline__ uint64_t rot_to(uint64_t mask, int left) {
-  const int s = left & 63;
-  return s ? (mask >> s) | (mask << (64 - s)) : mask;
-}
-
-__device__ __forceinline__ void wave_fence() { __threadfence_block(); }
-
-__device__ __forceinline__ uint64_t fetch32(const uint32_t *P, int pos) {
-  const uint32_t *w = P + (pos >> 4);
-  const int s = (pos & 15) * 2;
-  const uint64_t lo = (uint64_t)w[0] | ((uint64_t)w[1] << 32);
-  uint64_t x = lo >> s;
-  if (s) x |= (uint64_t)w[2] << (64 - s);
-  return x;
-}
-
-__device__ __forceinline__ int code_at(const uint32_t *P, int pos) {
-  return (P[pos >> 4] >> ((pos & 15) * 2)) & 3;
-}
-
-// The inner while of Prefix_Edit_Dist (:226-227) from (row, row + d).
-__device__ __forceinline__ int slide(const uint32_t *A, int ab, const uint32_t *B, int bb, int row,
-                                     int d, int m, int n) {
-  const int rem = min(m - row, n - (row + d));
-  int adv = 0;
-  while (adv < rem) {
-    const uint64_t x = fetch32(A, ab + row + adv) ^ fetch32(B, bb + row + d + adv);
-    if (x) {
-      adv += __builtin_ctzll(x) >> 1;
-      break;
-    }
-    adv += 32;
-  }
-  return row + min(adv, rem);
-}
-
-struct RowMeta { int off, lo, hi; };   // value of (e, d) at log[off + d] for lo <= d <= hi, else -2
-
-__device__ __forceinline__ int row_get(const int32_t *log, const RowMeta M, int d) {
-  return (d >= M.lo && d <= M.hi) ? log[M.off + d] : -2;
-}
-
 __device__ __forceinline__ int error_bound(int i, double erate) {   // findErrors.C:476-477
   return (int)ceil((double)i * erate);
 }
@@ -216,237 +149,39 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 8) void k_fe_align(const Alig
   const int chg_cap = X.max_limit + 8;
 
   for (;;) {
-    uint32_t slot = 0;
-    if (lane == 0) slot = atomicAdd(X.next, 1u);
-    slot = (uint32_t)uni((int)slot);
+    const uint32_t slot = next_job(X.next, lane);
     if (slot >= X.njobs) break;
     const uint32_t oi = X.order[slot];
     const Job J = X.jobs[oi];
     const uint32_t *const A = X.fwd + J.a_word;           // the whole A read: the votes' bases
     const int m = J.m, n = J.n, ab = J.a_off;
     const int shorter = min(m, n);
-    uint32_t flags = 0, nrows = 0;
-    // the two spans the aligner reads: in LDS where both fit, else where they lie
+    // the two spans the aligner reads
     const uint32_t *As = A, *B = (J.b_rc ? X.rc : X.fwd) + J.b_word;
     int as = ab, bb = J.b_off;
-    // A row never passes min(m, n - d) and |d| <= limit: what lies beyond is never read
-    const int ma = min(m, n + J.limit), nb = min(n, m + J.limit);
-    if (max(ma, nb) <= FE_LDS_BASES) {
-      uint32_t *const la = s_strand[threadIdx.x >> 6][0], *const lb = s_strand[threadIdx.x >> 6][1];
-      const int wa = ((as & 15) + ma) / 16 + PAD_WORDS, wb = ((bb & 15) + nb) / 16 + PAD_WORDS;
-      for (int i = lane; i < wa; i += 64) la[i] = As[(as >> 4) + i];
-      for (int i = lane; i < wb; i += 64) lb[i] = B[(bb >> 4) + i];
-      wave_fence();
-      As = la; as &= 15;
-      B = lb; bb &= 15;
+    uint32_t flags = 0;
+    if (ped_stage<FE_LDS_BASES>(As, as, B, bb, m, n, J.limit, s_strand[threadIdx.x >> 6][0],
+                                s_strand[threadIdx.x >> 6][1], lane))
       flags |= F_STAGED;
-    }
 
-    int errors = 0, a_end = 0, b_end = 0, delta_len = 0;
-    bool to_end = false, aborted = false;
-
-    const int row0 = uni(slide(As, as, B, bb, 0, 0, m, n));
-    if (row0 == shorter) {                                     // :195-200
-      a_end = b_end = row0;
-      to_end = true;
-    } else {
-      if (lane == 0) { log[0] = row0; meta[0] = 0; meta[1] = 0; meta[2] = 0; }
-      RowMeta PM{0, 0, 0};                                     // the row before
-      uint64_t logpos = 1;
-      int left = 0, right = 0;
-      int best_d = 0, best_e = 0, longest = 0;
-      double max_score = 0.0;
-      int ms_len = 0, ms_d = 0, ms_e = 0;
-      int pv = lane == 0 ? row0 : -2;                          // row e-1 at this lane's diagonal
-      bool pv_valid = true;
-      int end_e = 0, end_d = 0, end_row = 0;
-      bool ended = false;
-
-      for (int e = 1; e <= J.limit; e++) {
-        left = max(left - 1, -e);
-        right = min(right + 1, e);
-        const int width = right - left + 1;
-        if (logpos + (uint64_t)width > X.log_cap) { aborted = true; break; }
-        const int off = (int)logpos - left;
-        const int lim = X.match_limit[e];
-        nrows++;
-        wave_fence();                                          // row e-1 and its meta are written
-        int new_left, new_right, row_max = 0, row_max_d = 0;
-        bool hit = false;
-        int hit_d = 0, hit_row = 0;
-
-        if (width <= FE_WINDOW_DIAGS) {
-          const int d = left + ((lane - left) & 63);
-          const bool active = d <= right;
-          if (!pv_valid) pv = row_get(log, PM, d);
-          const int lo_n = from_lower(pv), up_n = from_upper(pv);
-          int row = max(max(1 + pv, lo_n), up_n + 1);
-          if (active) {
-            row = slide(As, as, B, bb, row, d, m, n);
-            log[off + d] = row;
-          } else {
-            row = -2;
-          }
-          const uint64_t em = rot_to(__ballot(active && (row == m || row + d == n)), left);
-          if (em) {
-            hit = true;
-            hit_d = left + __builtin_ctzll(em);
-            hit_row = __builtin_amdgcn_readlane(row, hit_d & 63);
-          } else {
-            const bool keep = active && ((d < 0 ? row : row + d) >= lim);   // :253-271
-            const uint64_t km = rot_to(__ballot(keep), left);
-            if (km == 0) {
-              new_left = right + 1;
-              new_right = right;
-            } else {
-              new_left = left + __builtin_ctzll(km);
-              new_right = left + 63 - __builtin_clzll(km);
-              const bool in = active && d >= new_left && d <= new_right;
-              row_max = wave_max(in ? row : -2);
-              row_max_d = left + __builtin_ctzll(rot_to(__ballot(in && row == row_max), left));
-              pv = in ? row : -2;
-              pv_valid = true;
-            }
-          }
-        } else {
-          flags |= F_GENERIC;
-          pv_valid = false;
-          const int nchunk = (width + 63) >> 6;
-          // One pass: the pruning (:253-271) and the leftmost maximum of the pruned band
-          // (:275-280) are kept from the ballots of the computing pass.  `com` is the maximum
-          // over [new_left, new_right] so far, `pen` over what lies right of new_right and
-          // joins the band only if a later diagonal holds the limit.
-          new_left = right + 1;
-          new_right = right;
-          bool any = false;
-          int com_max = -2, com_d = 0, pen_max = -2, pen_d = 0;
-          for (int c = 0; c < nchunk && !hit; c++) {
-            const int base = left + c * 64;
-            const int d = base + lane;
-            const bool active = d <= right;
-            int row = -2;
-            if (active) {
-              row = max(max(1 + row_get(log, PM, d), row_get(log, PM, d - 1)),
-                        row_get(log, PM, d + 1) + 1);
-              row = slide(As, as, B, bb, row, d, m, n);
-              log[off + d] = row;
-            }
-            const uint64_t em = __ballot(active && (row == m || row + d == n));
-            if (em) {
-              hit = true;
-              const int l = __builtin_ctzll(em);
-              hit_d = base + l;
-              hit_row = __builtin_amdgcn_readlane(row, l);
-              break;
-            }
-            const uint64_t km = __ballot(active && ((d < 0 ? row : row + d) >= lim));
-            if (km) {
-              const int fk = __builtin_ctzll(km), lk = 63 - __builtin_clzll(km);
-              const bool in1 = active && lane >= (any ? 0 : fk) && lane <= lk;
-              const int mx1 = wave_max(in1 ? row : -2);
-              const int d1 = base + __builtin_ctzll(__ballot(in1 && row == mx1));
-              if (pen_max > com_max) { com_max = pen_max; com_d = pen_d; }   // strictly: leftmost
-              if (mx1 > com_max) { com_max = mx1; com_d = d1; }
-              if (!any) new_left = base + fk;
-              any = true;
-              new_right = base + lk;
-              const bool in2 = active && lane > lk;
-              pen_max = -2;
-              if (__ballot(in2)) {
-                pen_max = wave_max(in2 ? row : -2);
-                pen_d = base + __builtin_ctzll(__ballot(in2 && row == pen_max));
-              }
-            } else if (any) {
-              const int mx = wave_max(active ? row : -2);
-              if (mx > pen_max) {
-                pen_max = mx;
-                pen_d = base + __builtin_ctzll(__ballot(active && row == mx));
-              }
-            }
-          }
-          row_max = com_max;
-          row_max_d = com_d;
-        }
-
-        if (hit) {                                             // :233-250
-          if (hit_row == m && 1 + row_get(log, PM, hit_d + 1) == hit_row && hit_d < right)
-            hit_d++;                                           // the last error is a mismatch
-          ended = true;
-          end_e = e;
-          end_d = hit_d;
-          end_row = hit_row;
-          break;
-        }
-        left = new_left;
-        right = new_right;
-        if (lane == 0) { meta[3 * e] = off; meta[3 * e + 1] = left; meta[3 * e + 2] = right; }
-        PM = RowMeta{off, left, right};
-        logpos += (uint64_t)width;
-        if (left > right) break;
-        if (row_max > longest) {                               // :275-280
-          best_d = row_max_d;
-          best_e = e;
-          longest = row_max;
-        }
-        const int score = (int)((double)longest * 0.272 - (double)e);   // int32: truncated
-        if ((double)score > max_score &&
-            best_e <= error_bound(min(longest, longest + best_d), X.erate)) {
-          max_score = (double)score;
-          ms_len = longest;
-          ms_d = best_d;
-          ms_e = best_e;
-        }
-      }
-
-      if (!aborted) {
-        int te, td, trow;
-        if (ended) {
-          te = end_e; td = end_d; trow = end_row;
-          errors = end_e; a_end = end_row; b_end = end_row + end_d; to_end = true;
-        } else {                                               // :298-308
-          te = ms_e; td = ms_d; trow = ms_len;
-          errors = ms_e; a_end = ms_len; b_end = ms_len + ms_d; to_end = false;
-        }
-        // Compute_Delta (:30-76); every lane walks the same path, lane 0 writes the stack
-        wave_fence();
-        int last = trow, sl = 0, d = td;
-        for (int k = te; k > 0; k--) {
-          const RowMeta M{meta[3 * (k - 1)], meta[3 * (k - 1) + 1], meta[3 * (k - 1) + 2]};
-          int from = d;
-          int mx = 1 + row_get(log, M, d);
-          int j = row_get(log, M, d - 1);
-          if (j > mx) { from = d - 1; mx = j; }
-          j = 1 + row_get(log, M, d + 1);
-          if (j > mx) { from = d + 1; mx = j; }
-          if (from == d - 1) {
-            if (lane == 0) stk[sl] = mx - last - 1;
-            sl++;
-            d--;
-            last = row_get(log, M, from);
-          } else if (from == d + 1) {
-            if (lane == 0) stk[sl] = last - (mx - 1);
-            sl++;
-            d++;
-            last = row_get(log, M, from);
-          }
-        }
-        if (lane == 0) stk[sl] = last + 1;
-        sl++;
-        wave_fence();
-        delta_len = sl - 1;
-        for (int k = lane; k < delta_len; k += 64) {
-          const int i = sl - 1 - k;
-          const int v = stk[i], s = stk[i - 1];
-          delta[k] = abs(v) * ((s > 0) - (s < 0));
-        }
-        wave_fence();
-      }
-    }
-
-    if (aborted) {
-      if (lane == 0) { X.flags[oi] = F_OVERFLOW | flags; X.rows[oi] = nrows; }
+    const double erate = X.erate;
+    const PedRows R = ped_rows(
+        As, as, B, bb, m, n, J.limit, X.match_limit, log, meta, X.log_cap, lane,
+        [erate](int score, double max_score, int longest, int best_d, int best_e) {
+          return (double)score > max_score &&
+                 best_e <= error_bound(min(longest, longest + best_d), erate);
+        });
+    if (R.generic) flags |= F_GENERIC;
+    if (R.aborted) {
+      if (lane == 0) { X.flags[oi] = F_OVERFLOW | flags; X.rows[oi] = R.nrows; }
       continue;
     }
+    // the alignment to the end, or else the one to the Max_Score cell (:298-308)
+    bool to_end = R.ended;
+    int errors, a_end, b_end;
+    if (to_end) { errors = R.end_e; a_end = R.end_row; b_end = R.end_row + R.end_d; }
+    else { errors = R.ms_e; a_end = R.ms_len; b_end = R.ms_len + R.ms_d; }
+    const int delta_len = ped_delta(log, meta, stk, delta, errors, b_end - a_end, a_end, lane);
 
     int olap_len = shorter;
     if (!to_end && a_end + ab >= J.clear_len - 1) {            // Process_Olap :149-152
@@ -547,29 +282,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 8) void k_fe_align(const Alig
         }
       }
     }
-    if (lane == 0) { X.flags[oi] = flags; X.rows[oi] = nrows; }
+    if (lane == 0) { X.flags[oi] = flags; X.rows[oi] = R.nrows; }
   }
 }
 
 // ------------------------------------------------------------------ the decision
-
-__device__ __forceinline__ int block_scan_incl(int v, int *lds, int &total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int s = 1; s < 64; s <<= 1) {
-    const int t = __shfl_up(v, s);
-    if (lane >= s) v += t;
-  }
-  __syncthreads();
-  if (lane == 63) lds[w] = v;
-  __syncthreads();
-  int add = 0, tot = 0;
-  for (int k = 0; k < (int)(blockDim.x >> 6); k++) {
-    if (k < w) add += lds[k];
-    tot += lds[k];
-  }
-  total = tot;
-  return v + add;
-}
 
 struct DecideArgs {
   int32_t *tallies;
@@ -668,85 +385,6 @@ __global__ __launch_bounds__(256) void k_fe_decide(const DecideArgs X) {
     }
   }
 }
-
-// ------------------------------------------------------------------ Edit_Match_Limit
-
-// Binomial_Bound.C:47 and Initialize_Match_Limit (:116), as findErrors.C:472-474 calls it.
-int binomial_bound(int e, double p, int start) {
-  const double bound = 1e-4, thold = 3.62;
-  const double q = 1.0 - p;
-  if (start < e) start = e;
-  for (int n = start; n < (int)AS_MAX_READLEN; n++) {
-    if (n <= 35) {
-      double sum = 0.0, p_pow = 1.0, q_pow = pow(q, n);
-      int bin = 1, ct = 0;
-      for (int k = 0; k < e && 1.0 - sum > bound; k++) {
-        const double x = bin * p_pow * q_pow;
-        sum += x;
-        bin *= n - ct;
-        bin /= ++ct;
-        p_pow *= p;
-        q_pow /= q;
-      }
-      if (1.0 - sum > bound) return n;
-    } else {
-      const double z = (e - 0.5 - n * p) / sqrt(n * p * q);
-      if (z <= thold) return n;
-      double sum = 0.0, mu_pow = 1.0, fact = 1.0;
-      const double pc = exp(-n * p);
-      for (int k = 0; k < e; k++) {
-        sum += mu_pow * pc / fact;
-        mu_pow *= n * p;
-        fact *= k + 1;
-      }
-      if (1.0 - sum > bound) return n;
-    }
-  }
-  return AS_MAX_READLEN;
-}
-
-void init_match_limit(std::vector<int32_t> &ml, double erate, int32_t max_errors, int32_t upto) {
-  ml.assign((size_t)upto + 1, 0);
-  int32_t e = 0, s = 1;
-  const int32_t l = std::min<int32_t>(max_errors, 2000);
-  while (e <= 1 && e <= upto) ml[e++] = 0;
-  while (e < l && e <= upto) {
-    s = binomial_bound(e - 1, erate, s);
-    ml[e] = s - 1;
-    e++;
-  }
-  if (e > upto) return;
-  const double sl = 0.982064188397525 / erate + 0.067835741959926;   // AS_MAX_READLEN_BITS 21
-  double vl = ml[e - 1] + sl;
-  while (e < max_errors && e <= upto) {
-    ml[e] = (int32_t)ceil(vl);
-    vl += sl;
-    e++;
-  }
-}
-
-template <class T>
-struct DevBuf {
-  T *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T));
-  }
-};
-
-struct Event {               // a hipEvent_t that is destroyed on every way out
-  hipEvent_t e = nullptr;
-  Event() = default;
-  Event(const Event &) = delete;
-  Event &operator=(const Event &) = delete;
-  ~Event() { if (e) (void)hipEventDestroy(e); }
-  hipError_t create() { return hipEventCreate(&e); }
-  operator hipEvent_t() const { return e; }
-};
 
 int check_params(const fe_params *p) {
   if (!p) return fail(FE_ERR_BAD_PARAM, "null parameters");
@@ -1012,8 +650,7 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
     if (const char *e = getenv("CANU_FE_LOG_PER_ERROR")) per_error = std::max(1, atoi(e));
     std::vector<uint32_t> todo = order, fl(n), rows(n);
     int32_t cur_limit = max_limit;
-    const uint64_t worst = ((uint64_t)max_limit + 1) * ((uint64_t)max_limit + 1) + 64;
-    uint64_t log_cap = std::min<uint64_t>((uint64_t)per_error * max_limit + 64, worst);
+    uint64_t log_cap = row_log_first(per_error, max_limit);
     // test knob: the exact size of the first row log
     if (const char *e = getenv("CANU_FE_LOG_CAP")) log_cap = std::max<uint64_t>(2, strtoull(e, nullptr, 10));
     Event e0, e1;
@@ -1028,7 +665,7 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
       const uint64_t fit = std::max<uint64_t>(1, SCRATCH_BUDGET / (per_wave * 4));
       const uint64_t nwaves = std::min<uint64_t>({nt, (uint64_t)c->n_cu * 8 * WAVES_PER_BLOCK, fit});
       const uint32_t blocks = (uint32_t)((nwaves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      if (log_cap > 0x7fff0000ull)
+      if (log_cap > ROW_LOG_MAX)
         return fail(FE_ERR_UNSUPPORTED, "a row log of %llu entries (%d errors allowed) is beyond "
                     "the 32-bit offsets of this build", (unsigned long long)log_cap, cur_limit);
       DevBuf<int32_t> d_scratch;
@@ -1069,11 +706,10 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
         }
       }
       if (!again.empty()) {
-        if (log_cap >= ((uint64_t)next_limit + 1) * ((uint64_t)next_limit + 1))
-          return fail(FE_ERR_HIP, "row log overflow at its worst-case size");
+        log_cap = row_log_regrown(log_cap, next_limit);
+        if (!log_cap) return fail(FE_ERR_HIP, "row log overflow at its worst-case size");
         c->S.regrows++;
         cur_limit = next_limit;
-        log_cap = ((uint64_t)next_limit + 1) * ((uint64_t)next_limit + 1) + 64;   // sum of 2e + 1
       }
       todo.swap(again);
     }

@@ -46,6 +46,7 @@
 
 #include "../../include/canu_fs.h"
 #include "fs_fasta.h"
+#include "hip_raii.h"
 
 namespace {
 
@@ -767,16 +768,6 @@ void free_reads(fs_ctx *c) {
   c->len.clear();
   c->off.clear();
 }
-
-template <class T> struct DevBuf {
-  T *p = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) {
-    bytes = std::max<size_t>(n, 1) * sizeof(T);
-    return hipMalloc((void **)&p, bytes);
-  }
-};
 
 // One batch of layouts on the device.
 int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &evs,

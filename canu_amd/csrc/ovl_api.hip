@@ -27,6 +27,7 @@
 #include "ovl_extend.hip"
 #include "ovl_ovb.h"
 #include "ovl_plan.h"
+#include "ped_host.h"
 
 using namespace ovl;
 
@@ -96,60 +97,8 @@ struct DBuf {
   }
 };
 
-static const uint32_t AS_MAX_READLEN = (1u << 21) - 1;
-
-// ---------------------------------------------------------------------------------------
-// maxErate tables (prefixEditDistance.C:40-116; Binomial_Bound.C:47 and :121)
-
-static int binomial_bound(int e, double p, int start) {
-  const double bound = 1e-4, thold = 3.62;
-  double q = 1.0 - p;
-  if (start < e) start = e;
-  for (int n = start; n < (int)AS_MAX_READLEN; n++) {
-    if (n <= 35) {
-      double sum = 0.0, p_pow = 1.0, q_pow = pow(q, n);
-      int bin = 1, ct = 0;
-      for (int k = 0; k < e && 1.0 - sum > bound; k++) {
-        double x = bin * p_pow * q_pow;
-        sum += x;
-        bin *= n - ct;
-        bin /= ++ct;
-        p_pow *= p;
-        q_pow /= q;
-      }
-      if (1.0 - sum > bound) return n;
-    } else {
-      double z = (e - 0.5 - n * p) / sqrt(n * p * q);
-      if (z <= thold) return n;
-      double sum = 0.0, mu_pow = 1.0, fact = 1.0, pc = exp(-n * p);
-      for (int k = 0; k < e; k++) {
-        sum += mu_pow * pc / fact;
-        mu_pow *= n * p;
-        fact *= k + 1;
-      }
-      if (1.0 - sum > bound) return n;
-    }
-  }
-  return AS_MAX_READLEN;
-}
-
-static void init_match_limit(std::vector<int32_t> &ml, double erate, int32_t max_errors) {
-  ml.assign(max_errors + 1, 0);
-  int32_t e = 0, s = 1, l = std::min<int32_t>(max_errors, 2000);
-  while (e <= 1) ml[e++] = 0;
-  while (e < l) {
-    s = binomial_bound(e - 1, erate, s);
-    ml[e] = s - 1;
-    e++;
-  }
-  double sl = 0.982064188397525 / erate + 0.067835741959926;   // AS_MAX_READLEN_BITS 21
-  double vl = ml[e - 1] + sl;
-  while (e < max_errors) {
-    ml[e] = (int32_t)ceil(vl);
-    vl += sl;
-    e++;
-  }
-}
+// the maxErate tables' Edit_Match_Limit (prefixEditDistance.C:40-116) is ped_host.h's
+using ped::AS_MAX_READLEN;
 
 // ---------------------------------------------------------------------------------------
 
@@ -620,7 +569,7 @@ int ovl_ctx_create(const ovl_params *p, int device, ovl_ctx **out) {
   for (uint32_t i = 0; i <= AS_MAX_READLEN; i++)
     c->h_error_bound[i] = (int32_t)ceil(i * er);
   std::vector<int32_t> ml;
-  init_match_limit(ml, er, c->max_errors);
+  ped::init_match_limit(ml, er, c->max_errors, c->max_errors);
   // padded past max_errors: the staged kernel may read its rows' limits straight from here
   // (OVL_GML), where a block's LDS copy held 0x7fffffff beyond max_errors
   ml.resize(ml.size() + 64, 0x7fffffff);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/canu_pair.h"
+#include "hip_raii.h"
 
 namespace {
 
@@ -463,12 +464,6 @@ void free_reads(pair_ctx *c) {
   c->len.clear();
   c->max_len = 0;
 }
-
-template <class T> struct DevBuf {
-  T *p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
 
 }  // namespace
 
