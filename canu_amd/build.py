@@ -98,6 +98,10 @@ FS_OUT = os.path.join(OUT_DIR, "libcanu_fs.so")
 FS_DEPS = _csrc("fs.hip", "fs_fasta.h", "hip_raii.h") + _inc("canu_fs.h")
 FS_CLI_OUT = os.path.join(BIN_DIR, "falconsense")
 
+TR_OUT = os.path.join(OUT_DIR, "libcanu_tr.so")
+TR_DEPS = _csrc("tr.hip", "hip_raii.h") + _inc("canu_tr.h", "canu_ovl.h")
+TR_CLI_OUT = os.path.join(BIN_DIR, "trimReads")
+
 
 def needs_build() -> bool:
     return _stale(OUT, OVL_DEPS)
@@ -193,11 +197,23 @@ def build_fs_cli(force: bool = False, verbose: bool = True) -> str:
                      force, verbose)
 
 
+def build_tr(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_tr.so: trimReads, overlap based trimming from the overlaps."""
+    return _hipcc_lib(TR_OUT, "tr.hip", TR_DEPS, force, verbose)
+
+
+def build_tr_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/trimReads: the command line canu's trimming stage runs."""
+    return _host_cli(TR_CLI_OUT, "tr_main.cpp", build_tr(verbose=verbose), "canu_tr",
+                     _csrc("gkp_store.h", "ovs_reader.h", "tr_files.h") +
+                     _inc("canu_tr.h", "canu_ovl.h"), force, verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
     build(force=force, profile="--profile" in sys.argv)
     if "--profile" not in sys.argv:
         for f in (build_mhap, build_cli, build_meryl, build_meryl_cli, build_emt_cli, build_pair,
                   build_pair_cli, build_fe, build_fe_cli, build_co, build_co_cli, build_fs,
-                  build_fs_cli):
+                  build_fs_cli, build_tr, build_tr_cli):
             f(force=force)
