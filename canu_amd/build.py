@@ -82,10 +82,12 @@ MERYL_CLI_OUT = os.path.join(BIN_DIR, "meryl")
 EMT_CLI_OUT = os.path.join(BIN_DIR, "estimate-mer-threshold")
 
 PAIR_OUT = os.path.join(OUT_DIR, "libcanu_pair.so")
-PAIR_DEPS = _csrc("pair.hip", "hip_raii.h") + _inc("canu_pair.h", "canu_ovl.h")
+CAPI_DEPS = _csrc("capi_common.h", "hip_raii.h")   # the C-API scaffold of the five libraries below
+PAIR_DEPS = _csrc("pair.hip") + CAPI_DEPS + _inc("canu_pair.h", "canu_ovl.h")
 PAIR_CLI_OUT = os.path.join(BIN_DIR, "overlapPair")
 
-PED_DEPS = _csrc("ped_wave.h", "ped_host.h", "hip_raii.h")   # the aligner fe.hip and co.hip share
+# the aligner fe.hip and co.hip share, and its host side
+PED_DEPS = _csrc("ped_wave.h", "ped_host.h", "ped_launch.h") + CAPI_DEPS
 FE_OUT = os.path.join(OUT_DIR, "libcanu_fe.so")
 FE_DEPS = _csrc("fe.hip") + PED_DEPS + _inc("canu_fe.h", "canu_ovl.h")
 FE_CLI_OUT = os.path.join(BIN_DIR, "findErrors")
@@ -95,11 +97,11 @@ CO_DEPS = _csrc("co.hip") + PED_DEPS + _inc("canu_co.h", "canu_fe.h", "canu_ovl.
 CO_CLI_OUT = os.path.join(BIN_DIR, "correctOverlaps")
 
 FS_OUT = os.path.join(OUT_DIR, "libcanu_fs.so")
-FS_DEPS = _csrc("fs.hip", "fs_fasta.h", "hip_raii.h") + _inc("canu_fs.h")
+FS_DEPS = _csrc("fs.hip", "fs_fasta.h") + CAPI_DEPS + _inc("canu_fs.h")
 FS_CLI_OUT = os.path.join(BIN_DIR, "falconsense")
 
 TR_OUT = os.path.join(OUT_DIR, "libcanu_tr.so")
-TR_DEPS = _csrc("tr.hip", "hip_raii.h") + _inc("canu_tr.h", "canu_ovl.h")
+TR_DEPS = _csrc("tr.hip") + CAPI_DEPS + _inc("canu_tr.h", "canu_ovl.h")
 TR_CLI_OUT = os.path.join(BIN_DIR, "trimReads")
 
 

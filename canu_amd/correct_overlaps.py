@@ -18,11 +18,12 @@ import struct
 
 import numpy as np
 
-from .find_errors import RED_DTYPE, _atof, _atoi
+from . import _capi
+from ._capi import _atof, _atoi
+from .find_errors import RED_DTYPE
 from .overlap_in_core import RECORD_DTYPE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "lib", "libcanu_co.so")
+LIB_PATH = _capi.lib_path("co")
 
 CO_STATUS = {0: "CO_OK", -1: "CO_ERR_NO_DEVICE", -2: "CO_ERR_BAD_PARAM",
              -3: "CO_ERR_UNSUPPORTED", -4: "CO_ERR_BAD_INPUT", -5: "CO_ERR_HIP",
@@ -44,10 +45,8 @@ COUNTERS = ("olaps_fwd", "olaps_rev", "total", "failed_both", "failed_either", "
 CORRECTED = ("corrected_bases", "substitutions", "deletions", "insertions")
 
 
-class CoError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"{CO_STATUS.get(code, code)}: {msg}")
-        self.code = code
+class CoError(_capi.CapiError):
+    STATUS = CO_STATUS
 
 
 class _Params(ctypes.Structure):
@@ -74,26 +73,11 @@ def load_library(path: str | None = None):
     if _lib is not None:
         return _lib
     path = path or os.environ.get("CANU_CO_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise CoError(-1, f"{path} missing: run __graft_entry__.build()")
-    lib = ctypes.CDLL(path)
-    if lib.co_abi_version() != ABI_VERSION:
-        raise CoError(-1, f"{path} has ABI {lib.co_abi_version()}, this binding expects "
-                          f"{ABI_VERSION}: rebuild with __graft_entry__.build()")
-    P, V, U32, U64 = ctypes.POINTER, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    lib.co_params_init.argtypes = [P(_Params)]
-    lib.co_params_init.restype = None
-    lib.co_last_error.restype = ctypes.c_char_p
-    lib.co_ctx_create.argtypes = [P(_Params), ctypes.c_int, P(V)]
-    lib.co_ctx_destroy.argtypes = [V]
-    lib.co_ctx_destroy.restype = None
-    lib.co_set_params.argtypes = [V, P(_Params)]
-    lib.co_load_reads.argtypes = [V, U32, U32, V, V, V]
-    lib.co_load_reads_device.argtypes = [V, U32, U32, V, V, V]
+    lib = _capi.load("co", path, ABI_VERSION, CoError, _Params, _Stats)
+    V, U32, U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
     lib.co_set_corrections.argtypes = [V, V, U64]
     lib.co_correct_overlaps.argtypes = [V, U32, U32, V, U64, V]
     lib.co_write_oea.argtypes = [V, ctypes.c_char_p]
-    lib.co_get_stats.argtypes = [V, P(_Stats)]
     _lib = lib
     return lib
 
@@ -156,52 +140,13 @@ def clamp_range(bgn: int, end: int, num_reads: int) -> tuple[int, int]:
     return (1 if bgn < 1 else bgn), (num_reads if num_reads < end else end)
 
 
-class CorrectOverlaps:
+class CorrectOverlaps(_capi.Context):
     """One correctOverlaps job on one gfx950 device: load reads, set the corrections, run ranges
     of overlaps."""
+    PREFIX, ERROR, PARAMS, STATS = "co", CoError, CoParameters, _Stats
 
     def __init__(self, params: CoParameters | None = None, device: int = 0):
-        self.lib = load_library()
-        self.params = params or CoParameters()
-        self.ctx = None
-        ctx = ctypes.c_void_p()
-        cp = self.params.to_c()
-        self._check(self.lib.co_ctx_create(ctypes.byref(cp), device, ctypes.byref(ctx)))
-        self.ctx = ctx
-
-    def _check(self, rc: int):
-        if rc != 0:
-            raise CoError(rc, self.lib.co_last_error().decode())
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.co_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, params: CoParameters) -> None:
-        cp = params.to_c()
-        self._check(self.lib.co_set_params(self.ctx, ctypes.byref(cp)))
-        self.params = params
-
-    def load_reads(self, rs) -> None:
-        bases = np.ascontiguousarray(rs.bases, dtype=np.uint8)
-        offs = np.ascontiguousarray(rs.offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(rs.lengths, dtype=np.uint32)
-        self._check(self.lib.co_load_reads(self.ctx, rs.first_iid, rs.nreads, bases.ctypes.data,
-                                           offs.ctypes.data, lens.ctypes.data))
-
-    def load_reads_device(self, first_iid: int, d_bases: int, d_offsets: int,
-                          lengths: np.ndarray) -> None:
-        """Reads already in HBM (device pointers, e.g. the buffers another stage loaded)."""
-        lens = np.ascontiguousarray(lengths, dtype=np.uint32)
-        self._check(self.lib.co_load_reads_device(self.ctx, first_iid, lens.shape[0], d_bases,
-                                                  d_offsets, lens.ctypes.data))
+        super().__init__(load_library(), params, device)
 
     def set_corrections(self, red: np.ndarray) -> None:
         """The records of a .red file (RED_DTYPE, what FindErrors.run returns), ascending by
@@ -222,11 +167,6 @@ class CorrectOverlaps:
 
     def write_oea(self, path: str) -> None:
         self._check(self.lib.co_write_oea(self.ctx, os.fsencode(path)))
-
-    def stats(self) -> dict:
-        s = _Stats()
-        self._check(self.lib.co_get_stats(self.ctx, ctypes.byref(s)))
-        return {n: getattr(s, n) for n, _ in _Stats._fields_}
 
     def counters(self) -> dict:
         s = self.stats()

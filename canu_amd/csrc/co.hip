@@ -23,56 +23,31 @@
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <string>
 #include <vector>
 
 #include "../../include/canu_co.h"
-#include "hip_raii.h"
-#include "ped_host.h"
+#include "capi_common.h"
+#include "ped_launch.h"
 #include "ped_wave.h"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(x)                                                                    \
-  do {                                                                                \
-    hipError_t e_ = (x);                                                              \
-    if (e_ != hipSuccess)                                                             \
-      return fail(e_ == hipErrorOutOfMemory ? CO_ERR_OOM : CO_ERR_HIP, "%s: %s", #x,  \
-                  hipGetErrorString(e_));                                             \
-  } while (0)
-
 using namespace ped;
+using capi::fail;
 
+CAPI_SAME_CODES(CO);
 static_assert(CO_WINDOW_DIAGS == PED_WINDOW_DIAGS, "canu_co.h names the aligner's window");
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr uint64_t SCRATCH_BUDGET = 16ull << 30;      // row logs of one launch, bytes
 constexpr uint64_t CORRECT_BUDGET = 4ull << 30;       // per-block work areas of k_co_correct
 constexpr int AS_MAX_EVALUE = 4095;                   // ovOverlap.H:41-42
 // Vote_Value_t (correctionOutput.H:24-37)
 enum { V_IDENT = 0, V_DELETE = 1, V_A_SUBST = 2, V_T_SUBST = 5, V_A_INSERT = 6, V_T_INSERT = 9 };
 // what k_co_correct thinks of a read
 enum : uint32_t { R_OK = 0, R_NO_IDENT = 1, R_BAD_POSITION = 2 };
-// per-overlap outcome
-enum : uint32_t { F_DONE = 1, F_TO_END = 2, F_OVERFLOW = 4, F_GENERIC = 8, F_INTERNAL = 16,
-                  F_STAGED = 32 };
+// per-overlap outcome, with ped_host.h's
+enum : uint32_t { F_DONE = 1, F_TO_END = 2 };
 // the nine counters, in the order Redo_Olaps prints them
 enum { C_FWD = 0, C_REV, C_TOTAL, C_BOTH, C_EITHER, C_END, C_LENGTH, C_RHA_FAIL, C_RHA_PASS, NCOUNT };
 constexpr int LDS_STRAND_WORDS = lds_strand_words(CO_LDS_BASES);
@@ -107,28 +82,6 @@ struct AlignArgs {
   uint64_t log_cap, per_wave;        // ints
   int32_t max_limit;
 };
-
-// ------------------------------------------------------------------ read encoding
-
-__global__ void k_co_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
-                            const uint64_t *__restrict__ word_off, const uint32_t *__restrict__ len,
-                            uint32_t nreads, uint32_t *__restrict__ fwd) {
-  for (uint32_t r = blockIdx.x; r < nreads; r += gridDim.x) {
-    const uint8_t *s = bases + src_off[r];
-    const uint32_t L = len[r];
-    const uint32_t nw = (L + 15) / 16;
-    for (uint32_t w = threadIdx.x; w < nw; w += blockDim.x) {
-      uint32_t f = 0;
-      for (uint32_t j = 0; j < 16; j++) {
-        const uint32_t i = w * 16 + j;
-        if (i >= L) break;
-        const uint8_t ch = s[i] | 0x20;
-        f |= (uint32_t)(ch == 'c' ? 1 : ch == 'g' ? 2 : ch == 't' ? 3 : 0) << (2 * j);   // the rest is 'a'
-      }
-      fwd[word_off[r] + w] = f;
-    }
-  }
-}
 
 // ------------------------------------------------------------------ the corrections
 
@@ -387,17 +340,9 @@ int check_params(const co_params *p) {
 
 }  // namespace
 
-struct co_ctx {
+struct co_ctx : capi::Device {
   co_params P;
-  int device = 0;
-  int n_cu = 256;
-  hipStream_t stream = nullptr;
-  // the reads as loaded
-  DevBuf<uint32_t> d_ofwd, d_len;
-  DevBuf<uint64_t> d_oword_off;
-  uint32_t first_iid = 0, nreads = 0;
-  std::vector<uint32_t> len;
-  std::vector<uint64_t> oword_off;
+  PackedReads reads;                 // as loaded: forward only, with the device tables
   // the corrected reads
   bool corrected = false;
   DevBuf<uint32_t> d_cfwd, d_crc, d_clen, d_adj_cnt;
@@ -406,8 +351,7 @@ struct co_ctx {
   std::vector<uint64_t> cword_off, adj_off;
   std::vector<uint32_t> clen, adj_cnt, status, changes;
   std::vector<Adjust> adj;
-  std::vector<int32_t> ml;           // Edit_Match_Limit, grown on demand
-  double ml_erate = -1.0;
+  MatchLimit ml;
   // the last result
   uint32_t bgn_id = 0, end_id = 0;
   std::vector<uint16_t> evalues;
@@ -424,14 +368,6 @@ void drop_corrections(co_ctx *c) {
   c->status.clear(); c->changes.clear(); c->adj.clear();
 }
 
-void free_reads(co_ctx *c) {
-  drop_corrections(c);
-  c->d_ofwd.release(); c->d_len.release(); c->d_oword_off.release();
-  c->nreads = 0;
-  c->len.clear();
-  c->oword_off.clear();
-}
-
 }  // namespace
 
 extern "C" {
@@ -441,42 +377,17 @@ void co_params_init(co_params *p) {
   p->error_rate = 0.06;          // correctOverlaps.H:271
 }
 
-const char *co_last_error(void) { return g_err.c_str(); }
+const char *co_last_error(void) { return capi::g_err.c_str(); }
 int co_abi_version(void) { return CO_ABI_VERSION; }
 
 int co_ctx_create(const co_params *p, int device, co_ctx **out) {
   if (!out) return fail(CO_ERR_BAD_PARAM, "null out");
   *out = nullptr;
   if (int rc = check_params(p)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(CO_ERR_NO_DEVICE, "no HIP device %d", device);
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(CO_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
-                prop.gcnArchName);
-  HIP_TRY(hipSetDevice(device));
-  co_ctx *c = new co_ctx;
-  c->device = device;
-  c->n_cu = prop.multiProcessorCount;
-  c->P = *p;
-  hipError_t e = hipStreamCreate(&c->stream);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(CO_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  *out = c;
-  return CO_OK;
+  return capi::create_ctx(p, device, out);
 }
 
-void co_ctx_destroy(co_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  free_reads(c);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
+void co_ctx_destroy(co_ctx *c) { capi::destroy_ctx(c); }
 
 int co_set_params(co_ctx *c, const co_params *p) {
   if (!c) return fail(CO_ERR_BAD_PARAM, "null context");
@@ -488,55 +399,19 @@ int co_set_params(co_ctx *c, const co_params *p) {
 int co_load_reads_device(co_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *d_bases,
                          const uint64_t *d_offsets, const uint32_t *h_lengths) {
   if (!c) return fail(CO_ERR_BAD_PARAM, "null context");
-  if (nreads && (!d_bases || !d_offsets || !h_lengths))
-    return fail(CO_ERR_BAD_PARAM, "null read buffers");
-  if ((uint64_t)first_iid + nreads > 0xffffffffull)
-    return fail(CO_ERR_BAD_PARAM, "read IDs beyond 32 bits");
+  if (int rc = capi::check_device_reads(first_iid, nreads, d_bases, d_offsets, h_lengths)) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  free_reads(c);
-  std::vector<uint64_t> woff(nreads);
-  uint64_t words = 0;
-  for (uint32_t i = 0; i < nreads; i++) {
-    if (h_lengths[i] > AS_MAX_READLEN)
-      return fail(CO_ERR_BAD_INPUT, "read %u is %u bases, beyond AS_MAX_READLEN", first_iid + i,
-                  h_lengths[i]);
-    woff[i] = words;
-    words += (h_lengths[i] + 15) / 16 + 1;
-  }
-  HIP_TRY(c->d_oword_off.alloc(nreads));
-  HIP_TRY(c->d_len.alloc(nreads));
-  HIP_TRY(c->d_ofwd.alloc(words));
-  HIP_TRY(hipMemsetAsync(c->d_ofwd.p, 0, std::max<uint64_t>(words, 1) * 4, c->stream));
-  if (nreads) {
-    HIP_TRY(hipMemcpyAsync(c->d_oword_off.p, woff.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
-    const uint32_t grid = std::min<uint32_t>(nreads, 4096);
-    hipLaunchKernelGGL(k_co_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets,
-                       c->d_oword_off.p, c->d_len.p, nreads, c->d_ofwd.p);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->first_iid = first_iid;
-  c->nreads = nreads;
-  c->len.assign(h_lengths, h_lengths + nreads);
-  c->oword_off = std::move(woff);
-  return CO_OK;
+  drop_corrections(c);
+  return pack_reads<false>(c->reads, c->stream, 1, true, first_iid, nreads, d_bases, d_offsets,
+                           h_lengths);
 }
 
 int co_load_reads(co_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
                   const uint64_t *offsets, const uint32_t *lengths) {
   if (!c) return fail(CO_ERR_BAD_PARAM, "null context");
-  if (nreads && (!bases || !offsets || !lengths))
-    return fail(CO_ERR_BAD_PARAM, "null read buffers");
-  HIP_TRY(hipSetDevice(c->device));
-  uint64_t bytes = 0;
-  for (uint32_t i = 0; i < nreads; i++) bytes = std::max(bytes, offsets[i] + lengths[i]);
   DevBuf<uint8_t> d_b;
   DevBuf<uint64_t> d_o;
-  HIP_TRY(d_b.alloc(bytes));
-  HIP_TRY(d_o.alloc(nreads));
-  if (bytes) HIP_TRY(hipMemcpy(d_b.p, bases, bytes, hipMemcpyHostToDevice));
-  if (nreads) HIP_TRY(hipMemcpy(d_o.p, offsets, nreads * 8ull, hipMemcpyHostToDevice));
+  if (int rc = capi::stage_reads(c->device, nreads, bases, offsets, lengths, d_b, d_o)) return rc;
   return co_load_reads_device(c, first_iid, nreads, d_b.p, d_o.p, lengths);
 }
 
@@ -546,7 +421,7 @@ int co_set_corrections(co_ctx *c, const fe_correction *red, uint64_t n) {
   HIP_TRY(hipSetDevice(c->device));
   drop_corrections(c);
   c->S.ms_correct = 0;
-  const uint32_t nr = c->nreads;
+  const uint32_t nr = c->reads.nreads;
   for (uint64_t k = 1; k < n; k++)
     if (red[k].read_id < red[k - 1].read_id)
       return fail(CO_ERR_BAD_INPUT, "corrections are not ascending by read: record %llu is of read "
@@ -561,8 +436,8 @@ int co_set_corrections(co_ctx *c, const fe_correction *red, uint64_t n) {
     uint64_t e = k + 1;
     while (e < n && red[e].read_id == red[k].read_id) e++;
     const uint32_t id = red[k].read_id;
-    if (id >= c->first_iid && id - c->first_iid < nr && ((red[k].word >> 2) & 15) == V_IDENT) {
-      const uint32_t r = id - c->first_iid;
+    if (id >= c->reads.first_iid && id - c->reads.first_iid < nr && ((red[k].word >> 2) & 15) == V_IDENT) {
+      const uint32_t r = id - c->reads.first_iid;
       status[r] = R_OK;
       rec_first[r] = k + 1;
       rec_cnt[r] = (uint32_t)std::min<uint64_t>(e - k - 1, 0xffffffffull);
@@ -578,13 +453,13 @@ int co_set_corrections(co_ctx *c, const fe_correction *red, uint64_t n) {
       indel += t == V_DELETE || (t >= V_A_INSERT && t <= V_T_INSERT);
     }
     cwoff[r] = words;
-    words += (c->len[r] + ins + 15) / 16 + PAD_WORDS;
+    words += (c->reads.len[r] + ins + 15) / 16 + PAD_WORDS;
     adj_off[r] = nadj;
     nadj += indel;
-    max_len = std::max<uint64_t>(max_len, c->len[r]);
-    max_out = std::max<uint64_t>(max_out, c->len[r] + ins);
-    if (c->len[r] + ins > 0x7ffffff0ull)
-      return fail(CO_ERR_BAD_INPUT, "read %u: %llu insertions", c->first_iid + r, (unsigned long long)ins);
+    max_len = std::max<uint64_t>(max_len, c->reads.len[r]);
+    max_out = std::max<uint64_t>(max_out, c->reads.len[r] + ins);
+    if (c->reads.len[r] + ins > 0x7ffffff0ull)
+      return fail(CO_ERR_BAD_INPUT, "read %u: %llu insertions", c->reads.first_iid + r, (unsigned long long)ins);
   }
   max_out += 1;
 
@@ -624,7 +499,7 @@ int co_set_corrections(co_ctx *c, const fe_correction *red, uint64_t n) {
     HIP_TRY(hipMemcpyAsync(d_status.p, status.data(), nr * 4ull, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_adj_off.p, adj_off.data(), nr * 8ull, hipMemcpyHostToDevice, c->stream));
     CorrectArgs X{};
-    X.ofwd = c->d_ofwd.p; X.oword_off = c->d_oword_off.p; X.len = c->d_len.p; X.nreads = nr;
+    X.ofwd = c->reads.fwd.p; X.oword_off = c->reads.d_word_off.p; X.len = c->reads.d_len.p; X.nreads = nr;
     X.red = d_red.p; X.rec_first = d_rec_first.p; X.rec_cnt = d_rec_cnt.p;
     X.delta = d_delta.p; X.op = d_op.p; X.cbytes = d_cb.p; X.max_len = max_len; X.max_out = max_out;
     X.cfwd = c->d_cfwd.p; X.crc = c->d_crc.p; X.cword_off = d_cwoff.p; X.clen = c->d_clen.p;
@@ -666,15 +541,15 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
   c->S.ms_correct = ms_correct;
   c->evalues.clear();
   if (!c->corrected) return fail(CO_ERR_STATE, "no corrections: call co_set_corrections first");
-  if (bgn_id > end_id || bgn_id < c->first_iid || end_id - c->first_iid >= c->nreads)
+  if (bgn_id > end_id || bgn_id < c->reads.first_iid || end_id - c->reads.first_iid >= c->reads.nreads)
     return fail(CO_ERR_BAD_INPUT, "range %u-%u is not within the loaded reads %u-%u", bgn_id,
-                end_id, c->first_iid, c->first_iid + c->nreads - 1);
+                end_id, c->reads.first_iid, c->reads.first_iid + c->reads.nreads - 1);
   HIP_TRY(hipSetDevice(c->device));
   const double erate = c->P.error_rate;
   const uint64_t HM = (1ull << 21) - 1;
 
   auto refused = [&](uint32_t id) -> int {
-    const uint32_t st = c->status[id - c->first_iid];
+    const uint32_t st = c->status[id - c->reads.first_iid];
     if (st == R_NO_IDENT)
       return fail(CO_ERR_BAD_INPUT, "read %u has no IDENT record among the corrections", id);
     if (st == R_BAD_POSITION)
@@ -686,7 +561,7 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
   // Correct_Frags wants every read of the range (:287-296)
   for (uint32_t id = bgn_id; id <= end_id; id++) {
     if (int rc = refused(id)) return rc;
-    const uint32_t r = id - c->first_iid;
+    const uint32_t r = id - c->reads.first_iid;
     c->S.corrected_bases += (uint64_t)c->clen[r] + 1;
     c->S.substitutions += c->changes[3ull * r];
     c->S.deletions += c->changes[3ull * r + 1];
@@ -695,17 +570,16 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
   }
 
   std::vector<Job> jobs(n);
-  int32_t max_limit = 0;
   for (uint64_t i = 0; i < n; i++) {
     const uint32_t a = ov[i].a_iid, b = ov[i].b_iid;
     if (a < bgn_id || a > end_id)
       return fail(CO_ERR_BAD_INPUT, "overlap %llu: a_iid %u is outside the range %u-%u",
                   (unsigned long long)i, a, bgn_id, end_id);
-    if (b < c->first_iid || b - c->first_iid >= c->nreads)
+    if (b < c->reads.first_iid || b - c->reads.first_iid >= c->reads.nreads)
       return fail(CO_ERR_BAD_INPUT, "overlap %llu names read %u, not loaded",
                   (unsigned long long)i, b);
     if (int rc = refused(b)) return rc;
-    const uint32_t ar = a - c->first_iid, br = b - c->first_iid;
+    const uint32_t ar = a - c->reads.first_iid, br = b - c->reads.first_iid;
     const int64_t a5 = ov[i].dat[0] & HM, b5 = ov[i].dat[1] & HM;
     const bool flipped = (ov[i].dat[0] >> 54) & 1;
     const int64_t a_hang = a5 - b5;                            // ovOverlap.H:227
@@ -733,7 +607,6 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
     J.limit = (int32_t)ceil((double)std::min(J.m, J.n) * erate);   // correctOverlaps.C:135-136
     J.b_rc = flipped;
     J.pad = 0;
-    max_limit = std::max(max_limit, J.limit);
     c->S.bases += (uint64_t)std::min(J.m, J.n);
   }
 
@@ -741,106 +614,33 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
   c->end_id = end_id;
   if (n == 0) return CO_OK;
 
-  if (c->ml_erate != erate || (int32_t)c->ml.size() < max_limit + 2) {
-    const int32_t max_errors = 1 + (int32_t)(uint32_t)(erate * AS_MAX_READLEN);
-    init_match_limit(c->ml, erate, max_errors, max_limit + 1);
-    c->ml_erate = erate;
-  }
-
-  std::vector<uint32_t> order(n);
-  std::iota(order.begin(), order.end(), 0u);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-    return std::min(jobs[x].m, jobs[x].n) > std::min(jobs[y].m, jobs[y].n);
-  });
-  DevBuf<Job> d_jobs;
-  DevBuf<uint32_t> d_order, d_next, d_flags, d_rows;
-  DevBuf<int32_t> d_ml, d_errors, d_olen;
+  DevBuf<int32_t> d_errors, d_olen;
   DevBuf<unsigned long long> d_counters;
-  HIP_TRY(d_jobs.alloc(n));
-  HIP_TRY(d_order.alloc(n));
-  HIP_TRY(d_next.alloc(1));
-  HIP_TRY(d_flags.alloc(n));
-  HIP_TRY(d_rows.alloc(n));
   HIP_TRY(d_errors.alloc(n));
   HIP_TRY(d_olen.alloc(n));
   HIP_TRY(d_counters.alloc(NCOUNT));
-  HIP_TRY(d_ml.alloc(c->ml.size()));
-  HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(Job), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemcpyAsync(d_ml.p, c->ml.data(), c->ml.size() * 4, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(d_flags.p, 0, n * 4, c->stream));
-  HIP_TRY(hipMemsetAsync(d_rows.p, 0, n * 4, c->stream));
   HIP_TRY(hipMemsetAsync(d_errors.p, 0, n * 4, c->stream));
   HIP_TRY(hipMemsetAsync(d_olen.p, 0, n * 4, c->stream));
   HIP_TRY(hipMemsetAsync(d_counters.p, 0, NCOUNT * sizeof(unsigned long long), c->stream));
 
-  int per_error = CO_LOG_PER_ERROR;
-  if (const char *e = getenv("CANU_CO_LOG_PER_ERROR")) per_error = std::max(1, atoi(e));
-  std::vector<uint32_t> todo = order, fl(n), rows(n);
-  int32_t cur_limit = max_limit;
-  uint64_t log_cap = row_log_first(per_error, max_limit);
-  // test knob: the exact size of the first row log
-  if (const char *e = getenv("CANU_CO_LOG_CAP")) log_cap = std::max<uint64_t>(2, strtoull(e, nullptr, 10));
-  Event e0, e1;
-  HIP_TRY(e0.create());
-  HIP_TRY(e1.create());
-  float ms_align = 0;
-  while (!todo.empty()) {
-    const uint64_t nt = todo.size();
-    const uint64_t per_wave = log_cap + 3ull * (cur_limit + 2) + 2ull * (cur_limit + 4) + 8;
-    // 64 VGPRs and 4 KB of LDS per wave: eight waves per SIMD fit, if their row logs fit the
-    // budget; no more waves (and logs) than overlaps, and one wave always
-    const uint64_t fit = std::max<uint64_t>(1, SCRATCH_BUDGET / (per_wave * 4));
-    const uint64_t nwaves = std::min<uint64_t>({nt, (uint64_t)c->n_cu * 8 * WAVES_PER_BLOCK, fit});
-    const uint32_t blocks = (uint32_t)((nwaves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-    if (log_cap > ROW_LOG_MAX)
-      return fail(CO_ERR_UNSUPPORTED, "a row log of %llu entries (%d errors allowed) is beyond "
-                  "the 32-bit offsets of this build", (unsigned long long)log_cap, cur_limit);
-    DevBuf<int32_t> d_scratch;
-    HIP_TRY(d_scratch.alloc(per_wave * nwaves));
-    c->S.scratch_bytes = per_wave * nwaves * 4;
-    HIP_TRY(hipMemcpyAsync(d_order.p, todo.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(d_next.p, 0, 4, c->stream));
+  const AlignStage stage{"CANU_CO_LOG_PER_ERROR", "CANU_CO_LOG_CAP", CO_LOG_PER_ERROR, 0, 0, F_DONE,
+                         "the device adjusted its hang differently"};
+  std::vector<uint32_t> fl;
+  AlignStats A;
+  const int rc = align_all(*c, stage, c->ml, erate, jobs, [&](const AlignLaunch<Job> &L) {
     AlignArgs X{};
-    X.fwd = c->d_cfwd.p; X.rc = c->d_crc.p; X.jobs = d_jobs.p; X.order = d_order.p;
-    X.njobs = (uint32_t)nt; X.nwaves = (uint32_t)nwaves; X.next = d_next.p;
-    X.flags = d_flags.p; X.rows = d_rows.p; X.errors = d_errors.p; X.olap_len = d_olen.p;
+    X.fwd = c->d_cfwd.p; X.rc = c->d_crc.p; X.jobs = L.jobs; X.order = L.order;
+    X.njobs = L.njobs; X.nwaves = L.nwaves; X.next = L.next;
+    X.flags = L.flags; X.rows = L.rows; X.errors = d_errors.p; X.olap_len = d_olen.p;
     X.counters = d_counters.p; X.adj = c->d_adj.p; X.adj_off = c->d_adj_off.p;
-    X.adj_cnt = c->d_adj_cnt.p; X.clen = c->d_clen.p; X.match_limit = d_ml.p;
-    X.scratch = d_scratch.p; X.log_cap = log_cap; X.per_wave = per_wave; X.max_limit = cur_limit;
-    HIP_TRY(hipEventRecord(e0, c->stream));
-    hipLaunchKernelGGL(k_co_align, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, c->stream, X);
-    hipError_t le = hipGetLastError();
-    HIP_TRY(hipEventRecord(e1, c->stream));
-    hipError_t se = hipStreamSynchronize(c->stream);
-    HIP_TRY(le);
-    HIP_TRY(se);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    ms_align += ms;
-    HIP_TRY(hipMemcpy(fl.data(), d_flags.p, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rows.data(), d_rows.p, n * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> again;
-    int32_t next_limit = 0;
-    for (uint32_t i : todo) {
-      c->S.rows += rows[i];
-      if (fl[i] & F_INTERNAL)
-        return fail(CO_ERR_HIP, "overlap %u: the device adjusted its hang differently", i);
-      if (fl[i] & F_OVERFLOW) {
-        again.push_back(i);
-        next_limit = std::max(next_limit, jobs[i].limit);
-      } else if (!(fl[i] & F_DONE)) {
-        return fail(CO_ERR_HIP, "overlap %u was not processed", i);
-      }
-    }
-    if (!again.empty()) {
-      log_cap = row_log_regrown(log_cap, next_limit);
-      if (!log_cap) return fail(CO_ERR_HIP, "row log overflow at its worst-case size");
-      c->S.regrows++;
-      cur_limit = next_limit;
-    }
-    todo.swap(again);
-  }
-  c->S.ms_align = ms_align;
+    X.adj_cnt = c->d_adj_cnt.p; X.clen = c->d_clen.p; X.match_limit = L.match_limit;
+    X.scratch = L.scratch; X.log_cap = L.log_cap; X.per_wave = L.per_wave; X.max_limit = L.max_limit;
+    hipLaunchKernelGGL(k_co_align, dim3(L.blocks), dim3(64 * WAVES_PER_BLOCK), 0, c->stream, X);
+    return hipGetLastError();
+  }, fl, A);
+  c->S.n_generic = A.n_generic; c->S.n_staged = A.n_staged; c->S.rows = A.rows;
+  c->S.regrows = A.regrows; c->S.scratch_bytes = A.scratch_bytes; c->S.ms_align = A.ms_align;
+  if (rc) return rc;
 
   std::vector<int32_t> errors(n), olen(n);
   unsigned long long cnt[NCOUNT];
@@ -852,8 +652,6 @@ int co_correct_overlaps(co_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_r
   c->S.failed_length = cnt[C_LENGTH]; c->S.rha_fail = cnt[C_RHA_FAIL]; c->S.rha_pass = cnt[C_RHA_PASS];
   c->evalues.resize(n);
   for (uint64_t i = 0; i < n; i++) {
-    c->S.n_generic += !!(fl[i] & F_GENERIC);
-    c->S.n_staged += !!(fl[i] & F_STAGED);
     if (!(fl[i] & F_TO_END) || olen[i] <= 0) {                 // :485-516: the evalue stays
       c->evalues[i] = (uint16_t)((ov[i].dat[0] >> 42) & 0xfff);
     } else {                                                   // :521, ovOverlap.H:44-45

@@ -21,56 +21,31 @@
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <numeric>
-#include <string>
 #include <vector>
 
 #include "../../include/canu_fe.h"
-#include "hip_raii.h"
-#include "ped_host.h"
+#include "capi_common.h"
+#include "ped_launch.h"
 #include "ped_wave.h"
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(x)                                                                    \
-  do {                                                                                \
-    hipError_t e_ = (x);                                                              \
-    if (e_ != hipSuccess)                                                             \
-      return fail(e_ == hipErrorOutOfMemory ? FE_ERR_OOM : FE_ERR_HIP, "%s: %s", #x,  \
-                  hipGetErrorString(e_));                                             \
-  } while (0)
-
 using namespace ped;
+using capi::fail;
 
+CAPI_SAME_CODES(FE);
 static_assert(FE_WINDOW_DIAGS == PED_WINDOW_DIAGS, "canu_fe.h names the aligner's window");
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr uint64_t SCRATCH_BUDGET = 16ull << 30;      // row logs of one launch, bytes
 constexpr int MAX_VOTE = 255, MAX_DEGREE = 32767;     // findErrors.H:87-90
 constexpr int MIN_HAPLO_OCCURS = 3;                   // findErrors.H:102
 constexpr int NPLANES = 11;
 // Vote_Value_t (correctionOutput.H:24-37) and the tally plane of each vote
 enum { V_IDENT = 0, V_DELETE = 1, V_A_SUBST = 2, V_T_SUBST = 5, V_A_INSERT = 6 };
 enum { PL_CONFIRMED = 0, PL_DELETES = 1, PL_SUBST = 2, PL_NO_INSERT = 6, PL_INSERT = 7 };
-// per-overlap outcome
-enum : uint32_t { F_PASSED = 1, F_FAILED = 2, F_OVERFLOW = 4, F_GENERIC = 8, F_INTERNAL = 16,
-                  F_STAGED = 32 };
+// per-overlap outcome, with ped_host.h's
+enum : uint32_t { F_PASSED = 1, F_FAILED = 2 };
 constexpr int LDS_STRAND_WORDS = lds_strand_words(FE_LDS_BASES);
 
 struct Job {                 // one overlap, as Process_Olap sets it up (:72-119)
@@ -100,32 +75,6 @@ struct AlignArgs {
   double erate;
   int32_t kmer_len, vote_qualify_len, end_exclude_len;
 };
-
-// ------------------------------------------------------------------ read encoding
-
-__global__ void k_fe_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
-                            const uint64_t *__restrict__ word_off, const uint32_t *__restrict__ len,
-                            uint32_t nreads, uint32_t *__restrict__ fwd, uint32_t *__restrict__ rc) {
-  for (uint32_t r = blockIdx.x; r < nreads; r += gridDim.x) {
-    const uint8_t *s = bases + src_off[r];
-    const uint32_t L = len[r];
-    const uint32_t nw = (L + 15) / 16;
-    for (uint32_t w = threadIdx.x; w < nw; w += blockDim.x) {
-      uint32_t f = 0, v = 0;
-      for (uint32_t j = 0; j < 16; j++) {
-        const uint32_t i = w * 16 + j;
-        if (i >= L) break;
-        const uint8_t ch = s[i] | 0x20, cr = s[L - 1 - i] | 0x20;
-        const uint32_t c = ch == 'c' ? 1 : ch == 'g' ? 2 : ch == 't' ? 3 : 0;   // the rest is 'a'
-        const uint32_t d = cr == 'c' ? 1 : cr == 'g' ? 2 : cr == 't' ? 3 : 0;
-        f |= c << (2 * j);
-        v |= (3 - d) << (2 * j);
-      }
-      fwd[word_off[r] + w] = f;
-      rc[word_off[r] + w] = v;
-    }
-  }
-}
 
 __device__ __forceinline__ int error_bound(int i, double erate) {   // findErrors.C:476-477
   return (int)ceil((double)i * erate);
@@ -400,33 +349,13 @@ int check_params(const fe_params *p) {
 
 }  // namespace
 
-struct fe_ctx {
+struct fe_ctx : capi::Device {
   fe_params P;
-  int device = 0;
-  int n_cu = 256;
-  hipStream_t stream = nullptr;
-  uint32_t *d_fwd = nullptr, *d_rc = nullptr;
-  uint32_t first_iid = 0, nreads = 0;
-  std::vector<uint32_t> len;
-  std::vector<uint64_t> word_off;
-  std::vector<int32_t> ml;           // Edit_Match_Limit, grown on demand
-  double ml_erate = -1.0;
+  PackedReads reads;                 // forward and reverse complement
+  MatchLimit ml;
   std::vector<fe_correction> out;
   fe_stats S{};
 };
-
-namespace {
-
-void free_reads(fe_ctx *c) {
-  if (c->d_fwd) (void)hipFree(c->d_fwd);
-  if (c->d_rc) (void)hipFree(c->d_rc);
-  c->d_fwd = c->d_rc = nullptr;
-  c->nreads = 0;
-  c->len.clear();
-  c->word_off.clear();
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -440,42 +369,17 @@ void fe_params_init(fe_params *p) {
   p->use_haplo_ct = 1;
 }
 
-const char *fe_last_error(void) { return g_err.c_str(); }
+const char *fe_last_error(void) { return capi::g_err.c_str(); }
 int fe_abi_version(void) { return FE_ABI_VERSION; }
 
 int fe_ctx_create(const fe_params *p, int device, fe_ctx **out) {
   if (!out) return fail(FE_ERR_BAD_PARAM, "null out");
   *out = nullptr;
   if (int rc = check_params(p)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(FE_ERR_NO_DEVICE, "no HIP device %d", device);
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FE_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
-                prop.gcnArchName);
-  HIP_TRY(hipSetDevice(device));
-  fe_ctx *c = new fe_ctx;
-  c->device = device;
-  c->n_cu = prop.multiProcessorCount;
-  c->P = *p;
-  hipError_t e = hipStreamCreate(&c->stream);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(FE_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  *out = c;
-  return FE_OK;
+  return capi::create_ctx(p, device, out);
 }
 
-void fe_ctx_destroy(fe_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  free_reads(c);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
+void fe_ctx_destroy(fe_ctx *c) { capi::destroy_ctx(c); }
 
 int fe_set_params(fe_ctx *c, const fe_params *p) {
   if (!c) return fail(FE_ERR_BAD_PARAM, "null context");
@@ -487,59 +391,18 @@ int fe_set_params(fe_ctx *c, const fe_params *p) {
 int fe_load_reads_device(fe_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *d_bases,
                          const uint64_t *d_offsets, const uint32_t *h_lengths) {
   if (!c) return fail(FE_ERR_BAD_PARAM, "null context");
-  if (nreads && (!d_bases || !d_offsets || !h_lengths))
-    return fail(FE_ERR_BAD_PARAM, "null read buffers");
-  if ((uint64_t)first_iid + nreads > 0xffffffffull)
-    return fail(FE_ERR_BAD_PARAM, "read IDs beyond 32 bits");
+  if (int rc = capi::check_device_reads(first_iid, nreads, d_bases, d_offsets, h_lengths)) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  free_reads(c);
-  std::vector<uint64_t> woff(nreads);
-  uint64_t words = 0;
-  for (uint32_t i = 0; i < nreads; i++) {
-    if (h_lengths[i] > AS_MAX_READLEN)
-      return fail(FE_ERR_BAD_INPUT, "read %u is %u bases, beyond AS_MAX_READLEN", first_iid + i,
-                  h_lengths[i]);
-    woff[i] = words;
-    words += (h_lengths[i] + 15) / 16 + PAD_WORDS;
-  }
-  DevBuf<uint64_t> d_woff;
-  DevBuf<uint32_t> d_len;
-  HIP_TRY(d_woff.alloc(nreads));
-  HIP_TRY(d_len.alloc(nreads));
-  HIP_TRY(hipMalloc((void **)&c->d_fwd, std::max<uint64_t>(words, 1) * 4));
-  HIP_TRY(hipMalloc((void **)&c->d_rc, std::max<uint64_t>(words, 1) * 4));
-  HIP_TRY(hipMemsetAsync(c->d_fwd, 0, std::max<uint64_t>(words, 1) * 4, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_rc, 0, std::max<uint64_t>(words, 1) * 4, c->stream));
-  if (nreads) {
-    HIP_TRY(hipMemcpyAsync(d_woff.p, woff.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
-    const uint32_t grid = std::min<uint32_t>(nreads, 4096);
-    hipLaunchKernelGGL(k_fe_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets,
-                       d_woff.p, d_len.p, nreads, c->d_fwd, c->d_rc);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  c->first_iid = first_iid;
-  c->nreads = nreads;
-  c->len.assign(h_lengths, h_lengths + nreads);
-  c->word_off = std::move(woff);
-  return FE_OK;
+  return pack_reads<true>(c->reads, c->stream, PAD_WORDS, false, first_iid, nreads, d_bases,
+                          d_offsets, h_lengths);
 }
 
 int fe_load_reads(fe_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
                   const uint64_t *offsets, const uint32_t *lengths) {
   if (!c) return fail(FE_ERR_BAD_PARAM, "null context");
-  if (nreads && (!bases || !offsets || !lengths))
-    return fail(FE_ERR_BAD_PARAM, "null read buffers");
-  HIP_TRY(hipSetDevice(c->device));
-  uint64_t bytes = 0;
-  for (uint32_t i = 0; i < nreads; i++) bytes = std::max(bytes, offsets[i] + lengths[i]);
   DevBuf<uint8_t> d_b;
   DevBuf<uint64_t> d_o;
-  HIP_TRY(d_b.alloc(bytes));
-  HIP_TRY(d_o.alloc(nreads));
-  if (bytes) HIP_TRY(hipMemcpy(d_b.p, bases, bytes, hipMemcpyHostToDevice));
-  if (nreads) HIP_TRY(hipMemcpy(d_o.p, offsets, nreads * 8ull, hipMemcpyHostToDevice));
+  if (int rc = capi::stage_reads(c->device, nreads, bases, offsets, lengths, d_b, d_o)) return rc;
   return fe_load_reads_device(c, first_iid, nreads, d_b.p, d_o.p, lengths);
 }
 
@@ -548,12 +411,13 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
   if (!c) return fail(FE_ERR_BAD_PARAM, "null context");
   if (n && !ov) return fail(FE_ERR_BAD_PARAM, "null overlaps");
   if (n > 0xfffffff0ull) return fail(FE_ERR_BAD_PARAM, "more than 2^32 overlaps in one call");
+  const PackedReads &R = c->reads;
   c->S = fe_stats{};
   c->out.clear();
   if (n_corrections) *n_corrections = 0;
-  if (bgn_id > end_id || bgn_id < c->first_iid || end_id - c->first_iid >= c->nreads)
+  if (bgn_id > end_id || bgn_id < R.first_iid || end_id - R.first_iid >= R.nreads)
     return fail(FE_ERR_BAD_INPUT, "range %u-%u is not within the loaded reads %u-%u", bgn_id,
-                end_id, c->first_iid, c->first_iid + c->nreads - 1);
+                end_id, R.first_iid, R.first_iid + R.nreads - 1);
   HIP_TRY(hipSetDevice(c->device));
   const uint32_t nr = end_id - bgn_id + 1;
   const double erate = c->P.error_rate;
@@ -565,35 +429,34 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
   uint64_t plane = 0;
   for (uint32_t r = 0; r < nr; r++) {
     toff[r] = plane;
-    rlen[r] = c->len[bgn_id - c->first_iid + r];
-    rwoff[r] = c->word_off[bgn_id - c->first_iid + r];
+    rlen[r] = R.len[bgn_id - R.first_iid + r];
+    rwoff[r] = R.word_off[bgn_id - R.first_iid + r];
     plane += (uint64_t)rlen[r] + 1;
   }
 
   // Process_Olap's setup (:72-119), the checks the reference leaves out, and the degrees
   std::vector<Job> jobs(n);
   std::vector<uint64_t> ldeg(nr, 0), rdeg(nr, 0);
-  int32_t max_limit = 0;
   for (uint64_t i = 0; i < n; i++) {
     const uint32_t a = ov[i].a_iid, b = ov[i].b_iid;
     if (a < bgn_id || a > end_id)
       return fail(FE_ERR_BAD_INPUT, "overlap %llu: a_iid %u is outside the range %u-%u",
                   (unsigned long long)i, a, bgn_id, end_id);
-    if (b < c->first_iid || b - c->first_iid >= c->nreads)
+    if (b < R.first_iid || b - R.first_iid >= R.nreads)
       return fail(FE_ERR_BAD_INPUT, "overlap %llu names read %u, not loaded",
                   (unsigned long long)i, b);
     const int64_t a5 = ov[i].dat[0] & HM, a3 = (ov[i].dat[0] >> 21) & HM;
     const int64_t b5 = ov[i].dat[1] & HM, b3 = (ov[i].dat[1] >> 21) & HM;
     const bool flipped = (ov[i].dat[0] >> 54) & 1;
     const int64_t a_hang = a5 - b5, b_hang = b3 - a3;          // ovOverlap.H:227-228
-    const int64_t al = c->len[a - c->first_iid], bl = c->len[b - c->first_iid];
+    const int64_t al = R.len[a - R.first_iid], bl = R.len[b - R.first_iid];
     if (a_hang > al || -a_hang > bl)
       return fail(FE_ERR_BAD_INPUT, "overlap %llu: a_hang %lld beyond its read (%u: %lld bases, "
                   "%u: %lld bases)", (unsigned long long)i, (long long)a_hang, a, (long long)al, b,
                   (long long)bl);
     Job &J = jobs[i];
-    J.a_word = c->word_off[a - c->first_iid];
-    J.b_word = c->word_off[b - c->first_iid];
+    J.a_word = R.word_off[a - R.first_iid];
+    J.b_word = R.word_off[b - R.first_iid];
     J.tally = toff[a - bgn_id];
     J.a_off = a_hang > 0 ? (int32_t)a_hang : 0;
     J.b_off = a_hang < 0 ? (int32_t)-a_hang : 0;
@@ -603,7 +466,6 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
     J.limit = (int32_t)ceil((double)std::min(J.m, J.n) * erate);
     J.b_rc = flipped;
     J.pad = 0;
-    max_limit = std::max(max_limit, J.limit);
     if (a_hang <= 0) ldeg[a - bgn_id]++;
     if (b_hang >= 0) rdeg[a - bgn_id]++;
     c->S.bases += (uint64_t)std::min(J.m, J.n);
@@ -614,113 +476,35 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
               (g < (uint64_t)c->P.degree_threshold ? 2u : 0u);
   }
 
-  if (c->ml_erate != erate || (int32_t)c->ml.size() < max_limit + 2) {
-    const int32_t max_errors = 1 + (int32_t)(uint32_t)(erate * AS_MAX_READLEN);
-    init_match_limit(c->ml, erate, max_errors, max_limit + 1);
-    c->ml_erate = erate;
-  }
-
-  DevBuf<int32_t> d_tally, d_ml;
+  DevBuf<int32_t> d_tally;
   DevBuf<uint64_t> d_toff, d_rwoff, d_recoff;
   DevBuf<uint32_t> d_rlen, d_keep, d_count;
   HIP_TRY(d_tally.alloc(plane * NPLANES));
-  HIP_TRY(hipMemsetAsync(d_tally.p, 0, std::max<uint64_t>(plane * NPLANES, 1) * 4, c->stream));
-  float ms_align = 0;
+  HIP_TRY(hipMemsetAsync(d_tally.p, 0, d_tally.bytes, c->stream));
 
-  if (n) {
-    std::vector<uint32_t> order(n);
-    std::iota(order.begin(), order.end(), 0u);
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-      return std::min(jobs[x].m, jobs[x].n) > std::min(jobs[y].m, jobs[y].n);
-    });
-    DevBuf<Job> d_jobs;
-    DevBuf<uint32_t> d_order, d_next, d_flags, d_rows;
-    HIP_TRY(d_jobs.alloc(n));
-    HIP_TRY(d_order.alloc(n));
-    HIP_TRY(d_next.alloc(1));
-    HIP_TRY(d_flags.alloc(n));
-    HIP_TRY(d_rows.alloc(n));
-    HIP_TRY(d_ml.alloc(c->ml.size()));
-    HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(Job), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_ml.p, c->ml.data(), c->ml.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(d_flags.p, 0, n * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(d_rows.p, 0, n * 4, c->stream));
-
-    int per_error = FE_LOG_PER_ERROR;
-    if (const char *e = getenv("CANU_FE_LOG_PER_ERROR")) per_error = std::max(1, atoi(e));
-    std::vector<uint32_t> todo = order, fl(n), rows(n);
-    int32_t cur_limit = max_limit;
-    uint64_t log_cap = row_log_first(per_error, max_limit);
-    // test knob: the exact size of the first row log
-    if (const char *e = getenv("CANU_FE_LOG_CAP")) log_cap = std::max<uint64_t>(2, strtoull(e, nullptr, 10));
-    Event e0, e1;
-    HIP_TRY(e0.create());
-    HIP_TRY(e1.create());
-    while (!todo.empty()) {
-      const uint64_t nt = todo.size();
-      const uint64_t per_wave = log_cap + 3ull * (cur_limit + 2) + 2ull * (cur_limit + 4) +
-                                2ull * (cur_limit + 8) + 8;
-      // 64 VGPRs and 4 KB of LDS per wave: eight waves per SIMD fit, if their row logs fit the
-      // budget; no more waves (and logs) than overlaps, and one wave always
-      const uint64_t fit = std::max<uint64_t>(1, SCRATCH_BUDGET / (per_wave * 4));
-      const uint64_t nwaves = std::min<uint64_t>({nt, (uint64_t)c->n_cu * 8 * WAVES_PER_BLOCK, fit});
-      const uint32_t blocks = (uint32_t)((nwaves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK);
-      if (log_cap > ROW_LOG_MAX)
-        return fail(FE_ERR_UNSUPPORTED, "a row log of %llu entries (%d errors allowed) is beyond "
-                    "the 32-bit offsets of this build", (unsigned long long)log_cap, cur_limit);
-      DevBuf<int32_t> d_scratch;
-      HIP_TRY(d_scratch.alloc(per_wave * nwaves));
-      c->S.scratch_bytes = per_wave * nwaves * 4;
-      HIP_TRY(hipMemcpyAsync(d_order.p, todo.data(), nt * 4, hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipMemsetAsync(d_next.p, 0, 4, c->stream));
-      AlignArgs X{};
-      X.fwd = c->d_fwd; X.rc = c->d_rc; X.jobs = d_jobs.p; X.order = d_order.p;
-      X.njobs = (uint32_t)nt; X.nwaves = (uint32_t)nwaves; X.next = d_next.p; X.flags = d_flags.p; X.rows = d_rows.p;
-      X.tallies = d_tally.p; X.plane = plane; X.match_limit = d_ml.p; X.scratch = d_scratch.p;
-      X.log_cap = log_cap; X.per_wave = per_wave; X.max_limit = cur_limit; X.erate = erate;
-      X.kmer_len = c->P.kmer_len; X.vote_qualify_len = c->P.vote_qualify_len;
-      X.end_exclude_len = c->P.end_exclude_len;
-      HIP_TRY(hipEventRecord(e0, c->stream));
-      hipLaunchKernelGGL(k_fe_align, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, c->stream, X);
-      hipError_t le = hipGetLastError();
-      HIP_TRY(hipEventRecord(e1, c->stream));
-      hipError_t se = hipStreamSynchronize(c->stream);
-      HIP_TRY(le);
-      HIP_TRY(se);
-      float ms = 0;
-      (void)hipEventElapsedTime(&ms, e0, e1);
-      ms_align += ms;
-      HIP_TRY(hipMemcpy(fl.data(), d_flags.p, n * 4, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(rows.data(), d_rows.p, n * 4, hipMemcpyDeviceToHost));
-      std::vector<uint32_t> again;
-      int32_t next_limit = 0;
-      for (uint32_t i : todo) {
-        c->S.rows += rows[i];
-        if (fl[i] & F_INTERNAL)
-          return fail(FE_ERR_HIP, "overlap %u: the change list outgrew its errors", i);
-        if (fl[i] & F_OVERFLOW) {
-          again.push_back(i);
-          next_limit = std::max(next_limit, jobs[i].limit);
-        } else if (!(fl[i] & (F_PASSED | F_FAILED))) {
-          return fail(FE_ERR_HIP, "overlap %u was not processed", i);
-        }
-      }
-      if (!again.empty()) {
-        log_cap = row_log_regrown(log_cap, next_limit);
-        if (!log_cap) return fail(FE_ERR_HIP, "row log overflow at its worst-case size");
-        c->S.regrows++;
-        cur_limit = next_limit;
-      }
-      todo.swap(again);
-    }
-    for (uint64_t i = 0; i < n; i++) {
-      c->S.n_passed += !!(fl[i] & F_PASSED);
-      c->S.n_failed += !!(fl[i] & F_FAILED);
-      c->S.n_generic += !!(fl[i] & F_GENERIC);
-      c->S.n_staged += !!(fl[i] & F_STAGED);
-    }
+  // behind a wave's delta, k_fe_align's change list: limit + 8 changes of 2 ints
+  const AlignStage stage{"CANU_FE_LOG_PER_ERROR", "CANU_FE_LOG_CAP", FE_LOG_PER_ERROR, 2, 16,
+                         F_PASSED | F_FAILED, "the change list outgrew its errors"};
+  std::vector<uint32_t> fl;
+  AlignStats A;
+  const int rc = align_all(*c, stage, c->ml, erate, jobs, [&](const AlignLaunch<Job> &L) {
+    AlignArgs X{};
+    X.fwd = R.fwd.p; X.rc = R.rc.p; X.jobs = L.jobs; X.order = L.order;
+    X.njobs = L.njobs; X.nwaves = L.nwaves; X.next = L.next; X.flags = L.flags; X.rows = L.rows;
+    X.tallies = d_tally.p; X.plane = plane; X.match_limit = L.match_limit; X.scratch = L.scratch;
+    X.log_cap = L.log_cap; X.per_wave = L.per_wave; X.max_limit = L.max_limit; X.erate = erate;
+    X.kmer_len = c->P.kmer_len; X.vote_qualify_len = c->P.vote_qualify_len;
+    X.end_exclude_len = c->P.end_exclude_len;
+    hipLaunchKernelGGL(k_fe_align, dim3(L.blocks), dim3(64 * WAVES_PER_BLOCK), 0, c->stream, X);
+    return hipGetLastError();
+  }, fl, A);
+  c->S.n_generic = A.n_generic; c->S.n_staged = A.n_staged; c->S.rows = A.rows;
+  c->S.regrows = A.regrows; c->S.scratch_bytes = A.scratch_bytes; c->S.ms_align = A.ms_align;
+  if (rc) return rc;
+  for (uint32_t f : fl) {
+    c->S.n_passed += !!(f & F_PASSED);
+    c->S.n_failed += !!(f & F_FAILED);
   }
-  c->S.ms_align = ms_align;
 
   // the two ladders, then the records in file order
   HIP_TRY(d_toff.alloc(nr));
@@ -735,7 +519,7 @@ int fe_find_errors(fe_ctx *c, uint32_t bgn_id, uint32_t end_id, const ovl_record
   HIP_TRY(hipMemcpyAsync(d_keep.p, keep.data(), nr * 4ull, hipMemcpyHostToDevice, c->stream));
   DecideArgs D{};
   D.tallies = d_tally.p; D.plane = plane; D.tally_off = d_toff.p; D.word_off = d_rwoff.p;
-  D.len = d_rlen.p; D.keep = d_keep.p; D.fwd = c->d_fwd; D.bgn_id = bgn_id; D.nreads = nr;
+  D.len = d_rlen.p; D.keep = d_keep.p; D.fwd = R.fwd.p; D.bgn_id = bgn_id; D.nreads = nr;
   D.use_haplo_ct = c->P.use_haplo_ct; D.count = d_count.p; D.rec_off = d_recoff.p;
   Event e0, e1, e2, e3;
   HIP_TRY(e0.create());

@@ -37,39 +37,20 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../../include/canu_fs.h"
+#include "capi_common.h"
 #include "fs_fasta.h"
-#include "hip_raii.h"
 
 namespace {
 
-thread_local std::string g_err;
+using capi::fail;
 
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(x)                                                                  \
-  do {                                                                              \
-    hipError_t e_ = (x);                                                            \
-    if (e_ != hipSuccess)                                                           \
-      return fail(e_ == hipErrorOutOfMemory ? FS_ERR_OOM : FS_ERR_HIP, "%s: %s", #x, \
-                  hipGetErrorString(e_));                                           \
-  } while (0)
-
+CAPI_SAME_CODES(FS);
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr int STRIPE_ROWS = 4096;                     // 64 lanes x 64 rows
 constexpr int LDS_COLUMNS = 16384;                    // stripe-boundary row kept in LDS
@@ -734,14 +715,12 @@ void k_fs_consensus(const Tp *__restrict__ tps, const uint32_t n_tp,
 
 // ------------------------------------------------------------------ host
 
-struct fs_ctx {
-  int device = 0;
+struct fs_ctx : capi::Device {
   fs_params P{};
-  hipStream_t stream = nullptr;
   uint32_t first_iid = 0, nreads = 0;
   std::vector<uint32_t> len;
   std::vector<uint64_t> off;
-  uint8_t *d_fwd = nullptr, *d_rc = nullptr;
+  DevBuf<uint8_t> d_fwd, d_rc;
   // the last result
   bool have = false;
   std::vector<uint32_t> tig_ids;
@@ -761,9 +740,7 @@ int check_params(const fs_params *p) {
 }
 
 void free_reads(fs_ctx *c) {
-  if (c->d_fwd) (void)hipFree(c->d_fwd);
-  if (c->d_rc) (void)hipFree(c->d_rc);
-  c->d_fwd = c->d_rc = nullptr;
+  c->d_fwd.release(); c->d_rc.release();
   c->nreads = 0;
   c->len.clear();
   c->off.clear();
@@ -776,9 +753,7 @@ int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &e
   std::vector<Tp> tps = tps_in;
   const uint32_t n_tp = (uint32_t)tps.size(), n_ev = (uint32_t)evs.size();
   fs_stats &S = c->S;
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-  const uint32_t want_waves = (uint32_t)prop.multiProcessorCount * 4;
+  const uint32_t want_waves = (uint32_t)c->n_cu * 4;
   const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_ev + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
                                                                    want_waves / WAVES_PER_BLOCK));
   const uint64_t waves = (uint64_t)blocks * WAVES_PER_BLOCK;
@@ -847,13 +822,13 @@ int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &e
   hipEvent_t ev[5];
   for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
   HIP_TRY(hipEventRecord(ev[0], s));
-  hipLaunchKernelGGL(k_fs_locate, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd, c->d_rc,
+  hipLaunchKernelGGL(k_fs_locate, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd.p, c->d_rc.p,
                      d_ev.p, d_tp.p, n_ev, d_loc.p, d_cells.p, grow_words ? d_grow.p : nullptr,
                      grow_words, 1.0 - c->P.min_identity);
   hipError_t le = hipGetLastError();
   HIP_TRY(hipEventRecord(ev[1], s));
   if (le == hipSuccess) {
-    hipLaunchKernelGGL(k_fs_path, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd, c->d_rc,
+    hipLaunchKernelGGL(k_fs_path, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd.p, c->d_rc.p,
                        d_ev.p, d_tp.p, n_ev, d_loc.p, d_keys.p, d_vals.p, d_ntags.p, d_cells.p,
                        d_nleaf.p, d_nsplit.p, d_colP.p, d_colM.p, d_colS.p, d_endP.p, d_endM.p,
                        d_endS.p, d_ops.p, d_grow.p, max_blocks, ops_bytes, grow_words);
@@ -936,41 +911,17 @@ void fs_params_init(fs_params *p) {
   p->hbm_budget = 0;
 }
 
-const char *fs_last_error(void) { return g_err.c_str(); }
+const char *fs_last_error(void) { return capi::g_err.c_str(); }
 int fs_abi_version(void) { return FS_ABI_VERSION; }
 
 int fs_ctx_create(const fs_params *p, int device, fs_ctx **out) {
   if (!out) return fail(FS_ERR_BAD_PARAM, "null out");
   *out = nullptr;
   if (int rc = check_params(p)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(FS_ERR_NO_DEVICE, "no HIP device %d", device);
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(FS_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
-                prop.gcnArchName);
-  HIP_TRY(hipSetDevice(device));
-  fs_ctx *c = new fs_ctx;
-  c->device = device;
-  c->P = *p;
-  hipError_t e = hipStreamCreate(&c->stream);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(FS_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  *out = c;
-  return FS_OK;
+  return capi::create_ctx(p, device, out);
 }
 
-void fs_ctx_destroy(fs_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  free_reads(c);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
+void fs_ctx_destroy(fs_ctx *c) { capi::destroy_ctx(c); }
 
 int fs_set_params(fs_ctx *c, const fs_params *p) {
   if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
@@ -982,10 +933,7 @@ int fs_set_params(fs_ctx *c, const fs_params *p) {
 int fs_load_reads_device(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *d_bases,
                          const uint64_t *d_offsets, const uint32_t *h_lengths) {
   if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
-  if (nreads && (!d_bases || !d_offsets || !h_lengths))
-    return fail(FS_ERR_BAD_PARAM, "null read buffers");
-  if ((uint64_t)first_iid + nreads > 0xffffffffull)
-    return fail(FS_ERR_BAD_PARAM, "read IDs beyond 32 bits");
+  if (int rc = capi::check_device_reads(first_iid, nreads, d_bases, d_offsets, h_lengths)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   free_reads(c);
   c->have = false;
@@ -1003,8 +951,8 @@ int fs_load_reads_device(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const u
   HIP_TRY(bad.alloc(1));
   HIP_TRY(d_len.alloc(nreads));
   HIP_TRY(d_off.alloc(nreads));
-  HIP_TRY(hipMalloc((void **)&c->d_fwd, std::max<uint64_t>(total, 1)));
-  HIP_TRY(hipMalloc((void **)&c->d_rc, std::max<uint64_t>(total, 1)));
+  HIP_TRY(c->d_fwd.alloc(total));
+  HIP_TRY(c->d_rc.alloc(total));
   HIP_TRY(hipMemsetAsync(bad.p, 0, 4, c->stream));
   uint32_t h_bad = 0;
   if (nreads) {
@@ -1012,7 +960,7 @@ int fs_load_reads_device(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const u
     HIP_TRY(hipMemcpyAsync(d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
     const uint32_t grid = std::min<uint32_t>(nreads, 4096);
     hipLaunchKernelGGL(k_fs_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, d_off.p,
-                       d_len.p, nreads, c->d_fwd, c->d_rc, bad.p);
+                       d_len.p, nreads, c->d_fwd.p, c->d_rc.p, bad.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
@@ -1031,17 +979,9 @@ int fs_load_reads_device(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const u
 int fs_load_reads(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
                   const uint64_t *offsets, const uint32_t *lengths) {
   if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
-  if (nreads && (!bases || !offsets || !lengths))
-    return fail(FS_ERR_BAD_PARAM, "null read buffers");
-  HIP_TRY(hipSetDevice(c->device));
-  uint64_t bytes = 0;
-  for (uint32_t i = 0; i < nreads; i++) bytes = std::max(bytes, offsets[i] + lengths[i]);
   DevBuf<uint8_t> d_b;
   DevBuf<uint64_t> d_o;
-  HIP_TRY(d_b.alloc(bytes));
-  HIP_TRY(d_o.alloc(nreads));
-  if (bytes) HIP_TRY(hipMemcpy(d_b.p, bases, bytes, hipMemcpyHostToDevice));
-  if (nreads) HIP_TRY(hipMemcpy(d_o.p, offsets, nreads * 8ull, hipMemcpyHostToDevice));
+  if (int rc = capi::stage_reads(c->device, nreads, bases, offsets, lengths, d_b, d_o)) return rc;
   return fs_load_reads_device(c, first_iid, nreads, d_b.p, d_o.p, lengths);
 }
 

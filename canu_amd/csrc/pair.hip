@@ -18,39 +18,20 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <numeric>
-#include <string>
 #include <vector>
 
 #include "../../include/canu_pair.h"
-#include "hip_raii.h"
+#include "capi_common.h"
 
 namespace {
 
-thread_local std::string g_err;
+using capi::fail;
 
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(x)                                                                      \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess)                                                               \
-      return fail(e_ == hipErrorOutOfMemory ? PAIR_ERR_OOM : PAIR_ERR_HIP, "%s: %s", #x, \
-                  hipGetErrorString(e_));                                               \
-  } while (0)
-
+CAPI_SAME_CODES(PAIR);
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr int LDS_WORDS = PAIR_LDS_COLUMNS / 16;      // boundary row of one wave, 2 bits/column
 constexpr int MHAP_SLOP = 500;                         // overlapPair.C:64
@@ -427,16 +408,14 @@ void k_pair(const ReadTable R, const ovl_record *__restrict__ in, const uint32_t
 
 // ------------------------------------------------------------------ host
 
-struct pair_ctx {
-  int device = 0;
+struct pair_ctx : capi::Device {
   pair_params P{};
-  hipStream_t stream = nullptr;
   uint32_t first_iid = 0, nreads = 0;
   std::vector<uint32_t> len;
   uint32_t max_len = 0;
-  uint8_t *d_fwd = nullptr, *d_rc = nullptr;
-  uint64_t *d_off = nullptr;
-  uint32_t *d_len = nullptr;
+  DevBuf<uint8_t> d_fwd, d_rc;
+  DevBuf<uint64_t> d_off;
+  DevBuf<uint32_t> d_len;
   pair_stats S{};
 };
 
@@ -453,13 +432,7 @@ int check_params(const pair_params *p) {
 }
 
 void free_reads(pair_ctx *c) {
-  if (c->d_fwd) (void)hipFree(c->d_fwd);
-  if (c->d_rc) (void)hipFree(c->d_rc);
-  if (c->d_off) (void)hipFree(c->d_off);
-  if (c->d_len) (void)hipFree(c->d_len);
-  c->d_fwd = c->d_rc = nullptr;
-  c->d_off = nullptr;
-  c->d_len = nullptr;
+  c->d_fwd.release(); c->d_rc.release(); c->d_off.release(); c->d_len.release();
   c->nreads = 0;
   c->len.clear();
   c->max_len = 0;
@@ -477,41 +450,17 @@ void pair_params_init(pair_params *p) {
   p->invert = 0;
 }
 
-const char *pair_last_error(void) { return g_err.c_str(); }
+const char *pair_last_error(void) { return capi::g_err.c_str(); }
 int pair_abi_version(void) { return PAIR_ABI_VERSION; }
 
 int pair_ctx_create(const pair_params *p, int device, pair_ctx **out) {
   if (!out) return fail(PAIR_ERR_BAD_PARAM, "null out");
   *out = nullptr;
   if (int rc = check_params(p)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(PAIR_ERR_NO_DEVICE, "no HIP device %d", device);
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(PAIR_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
-                prop.gcnArchName);
-  HIP_TRY(hipSetDevice(device));
-  pair_ctx *c = new pair_ctx;
-  c->device = device;
-  c->P = *p;
-  hipError_t e = hipStreamCreate(&c->stream);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(PAIR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  *out = c;
-  return PAIR_OK;
+  return capi::create_ctx(p, device, out);
 }
 
-void pair_ctx_destroy(pair_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  free_reads(c);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
+void pair_ctx_destroy(pair_ctx *c) { capi::destroy_ctx(c); }
 
 int pair_set_params(pair_ctx *c, const pair_params *p) {
   if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
@@ -524,10 +473,7 @@ int pair_load_reads_device(pair_ctx *c, uint32_t first_iid, uint32_t nreads,
                            const uint8_t *d_bases, const uint64_t *d_offsets,
                            const uint32_t *h_lengths) {
   if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
-  if (nreads && (!d_bases || !d_offsets || !h_lengths))
-    return fail(PAIR_ERR_BAD_PARAM, "null read buffers");
-  if ((uint64_t)first_iid + nreads > 0xffffffffull)
-    return fail(PAIR_ERR_BAD_PARAM, "read IDs beyond 32 bits");
+  if (int rc = capi::check_device_reads(first_iid, nreads, d_bases, d_offsets, h_lengths)) return rc;
   HIP_TRY(hipSetDevice(c->device));
   free_reads(c);
   std::vector<uint64_t> off(nreads);
@@ -543,18 +489,18 @@ int pair_load_reads_device(pair_ctx *c, uint32_t first_iid, uint32_t nreads,
   }
   DevBuf<uint32_t> bad;
   HIP_TRY(bad.alloc(1));
-  HIP_TRY(hipMalloc((void **)&c->d_fwd, std::max<uint64_t>(total, 1)));
-  HIP_TRY(hipMalloc((void **)&c->d_rc, std::max<uint64_t>(total, 1)));
-  HIP_TRY(hipMalloc((void **)&c->d_off, std::max<size_t>(nreads, 1) * 8));
-  HIP_TRY(hipMalloc((void **)&c->d_len, std::max<size_t>(nreads, 1) * 4));
+  HIP_TRY(c->d_fwd.alloc(total));
+  HIP_TRY(c->d_rc.alloc(total));
+  HIP_TRY(c->d_off.alloc(nreads));
+  HIP_TRY(c->d_len.alloc(nreads));
   HIP_TRY(hipMemsetAsync(bad.p, 0, 4, c->stream));
   uint32_t h_bad = 0;
   if (nreads) {
-    HIP_TRY(hipMemcpyAsync(c->d_off, off.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_len, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_off.p, off.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
     const uint32_t grid = std::min<uint32_t>(nreads, 4096);
-    hipLaunchKernelGGL(k_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, c->d_off,
-                       c->d_len, nreads, c->d_fwd, c->d_rc, bad.p);
+    hipLaunchKernelGGL(k_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, c->d_off.p,
+                       c->d_len.p, nreads, c->d_fwd.p, c->d_rc.p, bad.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
   }
@@ -573,17 +519,9 @@ int pair_load_reads_device(pair_ctx *c, uint32_t first_iid, uint32_t nreads,
 int pair_load_reads(pair_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
                     const uint64_t *offsets, const uint32_t *lengths) {
   if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
-  if (nreads && (!bases || !offsets || !lengths))
-    return fail(PAIR_ERR_BAD_PARAM, "null read buffers");
-  HIP_TRY(hipSetDevice(c->device));
-  uint64_t bytes = 0;
-  for (uint32_t i = 0; i < nreads; i++) bytes = std::max(bytes, offsets[i] + lengths[i]);
   DevBuf<uint8_t> d_b;
   DevBuf<uint64_t> d_o;
-  HIP_TRY(d_b.alloc(bytes));
-  HIP_TRY(d_o.alloc(nreads));
-  if (bytes) HIP_TRY(hipMemcpy(d_b.p, bases, bytes, hipMemcpyHostToDevice));
-  if (nreads) HIP_TRY(hipMemcpy(d_o.p, offsets, nreads * 8ull, hipMemcpyHostToDevice));
+  if (int rc = capi::stage_reads(c->device, nreads, bases, offsets, lengths, d_b, d_o)) return rc;
   return pair_load_reads_device(c, first_iid, nreads, d_b.p, d_o.p, lengths);
 }
 
@@ -623,9 +561,7 @@ int pair_realign(pair_ctx *c, const ovl_record *in, uint64_t n, ovl_record *out)
   std::stable_sort(order.begin(), order.end(),
                    [&](uint32_t x, uint32_t y) { return est[x] > est[y]; });
 
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-  const uint64_t max_blocks = (uint64_t)prop.multiProcessorCount * 8;   // 8 waves per SIMD
+  const uint64_t max_blocks = (uint64_t)c->n_cu * 8;   // 8 waves per SIMD
   const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
                                                        max_blocks);
   const uint64_t scratch_words = need_scratch ? ((uint64_t)c->max_len + 15) / 16 : 0;
@@ -645,7 +581,7 @@ int pair_realign(pair_ctx *c, const ovl_record *in, uint64_t n, ovl_record *out)
   HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(d_flags.p, 0, n * 4, c->stream));
 
-  ReadTable R{c->d_fwd, c->d_rc, c->d_off, c->d_len, c->first_iid, c->nreads};
+  ReadTable R{c->d_fwd.p, c->d_rc.p, c->d_off.p, c->d_len.p, c->first_iid, c->nreads};
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));

@@ -88,4 +88,34 @@ inline uint64_t row_log_regrown(uint64_t log_cap, int32_t next_limit) {
   return log_cap >= row_log_rows(next_limit) ? 0 : row_log_worst(next_limit);
 }
 
+// What findErrors (fe.hip) and correctOverlaps (co.hip) launch the wave aligner with.
+constexpr int WAVES_PER_BLOCK = 4;
+constexpr uint64_t SCRATCH_BUDGET = 16ull << 30;      // row logs of one launch, bytes
+// the bits of a per-overlap outcome that mean the same in both; each stage has more of its own
+enum : uint32_t { F_OVERFLOW = 4, F_GENERIC = 8, F_INTERNAL = 16, F_STAGED = 32 };
+
+struct LaunchSize {
+  bool ok;                   // false: the log is beyond ROW_LOG_MAX and nothing was sized
+  uint64_t per_wave;         // ints of a wave's scratch: log, meta, stack, delta, the stage's own
+  uint64_t nwaves;           // waves that own scratch
+  uint32_t blocks;
+  uint64_t scratch_bytes;
+};
+
+// 64 VGPRs and 4 KB of LDS per wave: eight waves per SIMD fit, if their row logs fit the budget;
+// no more waves (and logs) than overlaps, and one wave always.  `extra` ints follow the delta.
+inline LaunchSize launch_size(uint64_t log_cap, int32_t limit, uint64_t extra, uint64_t todo,
+                              int n_cu, int waves_per_block = WAVES_PER_BLOCK,
+                              uint64_t budget = SCRATCH_BUDGET) {
+  LaunchSize L{};
+  if (log_cap > ROW_LOG_MAX) return L;
+  L.ok = true;
+  L.per_wave = log_cap + 3ull * (limit + 2) + 2ull * (limit + 4) + extra + 8;
+  const uint64_t fit = std::max<uint64_t>(1, budget / (L.per_wave * 4));
+  L.nwaves = std::min<uint64_t>({todo, (uint64_t)n_cu * 8 * waves_per_block, fit});
+  L.blocks = (uint32_t)((L.nwaves + waves_per_block - 1) / waves_per_block);
+  L.scratch_bytes = L.per_wave * L.nwaves * 4;
+  return L;
+}
+
 }  // namespace ped

@@ -25,14 +25,12 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "../../include/canu_tr.h"
-#include "hip_raii.h"
+#include "capi_common.h"
 
 #define TR_WAVE_CAP 512u      // overlaps of a read k_tr_wave holds in LDS (a power of two)
 #define AS_MAX_READLEN ((1u << 21) - 1)
@@ -40,25 +38,9 @@
 
 namespace {
 
-thread_local std::string g_err;
+using capi::fail;
 
-int fail(int code, const char *fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return code;
-}
-
-#define HIP_TRY(x)                                                                    \
-  do {                                                                                \
-    hipError_t e_ = (x);                                                              \
-    if (e_ != hipSuccess)                                                             \
-      return fail(e_ == hipErrorOutOfMemory ? TR_ERR_OOM : TR_ERR_HIP, "%s: %s", #x,  \
-                  hipGetErrorString(e_));                                             \
-  } while (0)
+CAPI_SAME_CODES(TR);
 
 enum { E_BAD_ID = 1, E_UNSORTED = 2, E_BAD_SPAN = 4 };
 enum { F_OK = 1, F_RESET = 2, F_LITERAL = 4 };           // k_tr_wave's flags of a read
@@ -553,11 +535,9 @@ int check_params(const tr_params *p) {
 
 }  // namespace
 
-struct tr_ctx {
-  int device = 0;
+struct tr_ctx : capi::Device {
   tr_params P{};
   tr_stats S{};
-  hipStream_t stream = nullptr;
 };
 
 extern "C" {
@@ -569,7 +549,7 @@ void tr_params_init(tr_params *p) {
   p->min_evidence_coverage = 1;
 }
 
-const char *tr_last_error(void) { return g_err.c_str(); }
+const char *tr_last_error(void) { return capi::g_err.c_str(); }
 int tr_abi_version(void) { return TR_ABI_VERSION; }
 uint32_t tr_wave_capacity(void) { return TR_WAVE_CAP; }
 
@@ -577,35 +557,10 @@ int tr_ctx_create(const tr_params *p, int device, tr_ctx **out) {
   if (!out) return fail(TR_ERR_BAD_PARAM, "no place for the context");
   *out = nullptr;
   if (int rc = check_params(p)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(TR_ERR_NO_DEVICE, "no HIP device");
-  if (device < 0 || device >= ndev)
-    return fail(TR_ERR_NO_DEVICE, "device %d of %d", device, ndev);
-  hipDeviceProp_t prop;
-  HIP_TRY(hipGetDeviceProperties(&prop, device));
-  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-    return fail(TR_ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
-                prop.gcnArchName);
-  HIP_TRY(hipSetDevice(device));
-  tr_ctx *c = new tr_ctx;
-  c->device = device;
-  c->P = *p;
-  hipError_t e = hipStreamCreate(&c->stream);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(TR_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
-  }
-  *out = c;
-  return TR_OK;
+  return capi::create_ctx(p, device, out);
 }
 
-void tr_ctx_destroy(tr_ctx *c) {
-  if (!c) return;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
-}
+void tr_ctx_destroy(tr_ctx *c) { capi::destroy_ctx(c); }
 
 int tr_set_params(tr_ctx *c, const tr_params *p) {
   if (!c) return fail(TR_ERR_STATE, "no context");

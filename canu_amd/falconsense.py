@@ -15,8 +15,9 @@ import re
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "lib", "libcanu_fs.so")
+from . import _capi
+
+LIB_PATH = _capi.lib_path("fs")
 
 FS_STATUS = {0: "FS_OK", -1: "FS_ERR_NO_DEVICE", -2: "FS_ERR_BAD_PARAM",
              -3: "FS_ERR_UNSUPPORTED", -4: "FS_ERR_BAD_INPUT", -5: "FS_ERR_HIP",
@@ -35,10 +36,8 @@ CHILD_DTYPE = np.dtype([("ident", "<u4"), ("reverse", "<u4"), ("min", "<i4"), ("
 COUNTERS = ("aligned", "skipped", "rejected")
 
 
-class FsError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"{FS_STATUS.get(code, code)}: {msg}")
-        self.code = code
+class FsError(_capi.CapiError):
+    STATUS = FS_STATUS
 
 
 class _Params(ctypes.Structure):
@@ -69,27 +68,12 @@ def load_library(path: str | None = None):
     if _lib is not None:
         return _lib
     path = path or os.environ.get("CANU_FS_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise FsError(-1, f"{path} missing: run __graft_entry__.build()")
-    lib = ctypes.CDLL(path)
-    if lib.fs_abi_version() != ABI_VERSION:
-        raise FsError(-1, f"{path} has ABI {lib.fs_abi_version()}, this binding expects "
-                          f"{ABI_VERSION}: rebuild with __graft_entry__.build()")
-    P, V, U32, U64 = ctypes.POINTER, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    lib.fs_params_init.argtypes = [P(_Params)]
-    lib.fs_params_init.restype = None
-    lib.fs_last_error.restype = ctypes.c_char_p
-    lib.fs_ctx_create.argtypes = [P(_Params), ctypes.c_int, P(V)]
-    lib.fs_ctx_destroy.argtypes = [V]
-    lib.fs_ctx_destroy.restype = None
-    lib.fs_set_params.argtypes = [V, P(_Params)]
-    lib.fs_load_reads.argtypes = [V, U32, U32, V, V, V]
-    lib.fs_load_reads_device.argtypes = [V, U32, U32, V, V, V]
+    lib = _capi.load("fs", path, ABI_VERSION, FsError, _Params, _Stats)
+    V, U64 = ctypes.c_void_p, ctypes.c_uint64
     lib.fs_consensus.argtypes = [V, V, U64, V, U64]
-    lib.fs_result_size.argtypes = [V, P(U64), P(U64)]
+    lib.fs_result_size.argtypes = [V, ctypes.POINTER(U64), ctypes.POINTER(U64)]
     lib.fs_fetch.argtypes = [V, V, V, V]
     lib.fs_write_fasta.argtypes = [V, ctypes.c_char_p]
-    lib.fs_get_stats.argtypes = [V, P(_Stats)]
     _lib = lib
     return lib
 
@@ -121,52 +105,13 @@ def fasta_of(tig_id: int, cns: bytes, min_output_length: int) -> bytes:
     return bytes(out)
 
 
-class FalconSense:
+class FalconSense(_capi.Context):
     """One falconsense job on one gfx950 device: load reads, run layouts."""
+    PREFIX, ERROR, PARAMS, STATS = "fs", FsError, FsParameters, _Stats
 
     def __init__(self, params: FsParameters | None = None, device: int = 0):
-        self.lib = load_library()
-        self.params = params or FsParameters()
-        self.ctx = None
         self._tigs = np.zeros(0, dtype=np.uint32)
-        ctx = ctypes.c_void_p()
-        cp = self.params.to_c()
-        self._check(self.lib.fs_ctx_create(ctypes.byref(cp), device, ctypes.byref(ctx)))
-        self.ctx = ctx
-
-    def _check(self, rc: int):
-        if rc != 0:
-            raise FsError(rc, self.lib.fs_last_error().decode())
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.fs_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, params: FsParameters) -> None:
-        cp = params.to_c()
-        self._check(self.lib.fs_set_params(self.ctx, ctypes.byref(cp)))
-        self.params = params
-
-    def load_reads(self, rs) -> None:
-        bases = np.ascontiguousarray(rs.bases, dtype=np.uint8)
-        offs = np.ascontiguousarray(rs.offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(rs.lengths, dtype=np.uint32)
-        self._check(self.lib.fs_load_reads(self.ctx, rs.first_iid, rs.nreads, bases.ctypes.data,
-                                           offs.ctypes.data, lens.ctypes.data))
-
-    def load_reads_device(self, first_iid: int, d_bases: int, d_offsets: int,
-                          lengths: np.ndarray) -> None:
-        """Reads already in HBM (device pointers, e.g. the buffers another stage loaded)."""
-        lens = np.ascontiguousarray(lengths, dtype=np.uint32)
-        self._check(self.lib.fs_load_reads_device(self.ctx, first_iid, lens.shape[0], d_bases,
-                                                  d_offsets, lens.ctypes.data))
+        super().__init__(load_library(), params, device)
 
     def run(self, layouts: np.ndarray, children: np.ndarray) -> list:
         """layouts: records with tig_id, first_child, n_children; children: records with ident,
@@ -203,11 +148,6 @@ class FalconSense:
     def counters(self) -> np.ndarray:
         """Per layout of the last run: evidence reads aligned, skipped, rejected."""
         return self._counts
-
-    def stats(self) -> dict:
-        s = _Stats()
-        self._check(self.lib.fs_get_stats(self.ctx, ctypes.byref(s)))
-        return {n: getattr(s, n) for n, _ in _Stats._fields_}
 
 
 def synth_layouts(n_templates: int, read_len: int = 4000, coverage: int = 12, err: float = 0.10,

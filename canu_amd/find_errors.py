@@ -11,14 +11,14 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import os
-import re
 
 import numpy as np
 
+from . import _capi
+from ._capi import _atof, _atoi  # noqa: F401  (other modules and tests take them from here)
 from .overlap_in_core import RECORD_DTYPE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "lib", "libcanu_fe.so")
+LIB_PATH = _capi.lib_path("fe")
 
 FE_STATUS = {0: "FE_OK", -1: "FE_ERR_NO_DEVICE", -2: "FE_ERR_BAD_PARAM",
              -3: "FE_ERR_UNSUPPORTED", -4: "FE_ERR_BAD_INPUT", -5: "FE_ERR_HIP",
@@ -36,10 +36,8 @@ VOTE_NAMES = ("IDENT", "DELETE", "A_SUBST", "C_SUBST", "G_SUBST", "T_SUBST", "A_
               "C_INSERT", "G_INSERT", "T_INSERT", "NO_VOTE", "EXTENSION")
 
 
-class FeError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"{FE_STATUS.get(code, code)}: {msg}")
-        self.code = code
+class FeError(_capi.CapiError):
+    STATUS = FE_STATUS
 
 
 class _Params(ctypes.Structure):
@@ -68,26 +66,11 @@ def load_library(path: str | None = None):
     if _lib is not None:
         return _lib
     path = path or os.environ.get("CANU_FE_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise FeError(-1, f"{path} missing: run __graft_entry__.build()")
-    lib = ctypes.CDLL(path)
-    if lib.fe_abi_version() != ABI_VERSION:
-        raise FeError(-1, f"{path} has ABI {lib.fe_abi_version()}, this binding expects "
-                          f"{ABI_VERSION}: rebuild with __graft_entry__.build()")
-    P, V, U32, U64 = ctypes.POINTER, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    lib.fe_params_init.argtypes = [P(_Params)]
-    lib.fe_params_init.restype = None
-    lib.fe_last_error.restype = ctypes.c_char_p
-    lib.fe_ctx_create.argtypes = [P(_Params), ctypes.c_int, P(V)]
-    lib.fe_ctx_destroy.argtypes = [V]
-    lib.fe_ctx_destroy.restype = None
-    lib.fe_set_params.argtypes = [V, P(_Params)]
-    lib.fe_load_reads.argtypes = [V, U32, U32, V, V, V]
-    lib.fe_load_reads_device.argtypes = [V, U32, U32, V, V, V]
-    lib.fe_find_errors.argtypes = [V, U32, U32, V, U64, P(U64)]
-    lib.fe_fetch_corrections.argtypes = [V, V, U64, P(U64)]
+    lib = _capi.load("fe", path, ABI_VERSION, FeError, _Params, _Stats)
+    V, U32, U64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
+    lib.fe_find_errors.argtypes = [V, U32, U32, V, U64, ctypes.POINTER(U64)]
+    lib.fe_fetch_corrections.argtypes = [V, V, U64, ctypes.POINTER(U64)]
     lib.fe_write_red.argtypes = [V, ctypes.c_char_p]
-    lib.fe_get_stats.argtypes = [V, P(_Stats)]
     _lib = lib
     return lib
 
@@ -106,16 +89,6 @@ class FeParameters:
         return _Params(float(self.error_rate), int(self.degree_threshold), int(self.kmer_len),
                        int(self.vote_qualify_len), int(self.end_exclude_len),
                        1 if self.use_haplo_ct else 0)
-
-
-def _atoi(s: str) -> int:
-    m = re.match(r"\s*[+-]?\d+", s)
-    return int(m.group(0)) if m else 0
-
-
-def _atof(s: str) -> float:
-    m = re.match(r"\s*[+-]?(\d+\.?\d*([eE][+-]?\d+)?|\.\d+([eE][+-]?\d+)?)", s)
-    return float(m.group(0)) if m else 0.0
 
 
 def parse_findErrors_args(argv: list[str]) -> tuple[FeParameters, dict]:
@@ -172,51 +145,12 @@ def parse_findErrors_args(argv: list[str]) -> tuple[FeParameters, dict]:
     return P, job
 
 
-class FindErrors:
+class FindErrors(_capi.Context):
     """One findErrors job on one gfx950 device: load reads, run ranges of overlaps."""
+    PREFIX, ERROR, PARAMS, STATS = "fe", FeError, FeParameters, _Stats
 
     def __init__(self, params: FeParameters | None = None, device: int = 0):
-        self.lib = load_library()
-        self.params = params or FeParameters()
-        self.ctx = None
-        ctx = ctypes.c_void_p()
-        cp = self.params.to_c()
-        self._check(self.lib.fe_ctx_create(ctypes.byref(cp), device, ctypes.byref(ctx)))
-        self.ctx = ctx
-
-    def _check(self, rc: int):
-        if rc != 0:
-            raise FeError(rc, self.lib.fe_last_error().decode())
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.fe_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, params: FeParameters) -> None:
-        cp = params.to_c()
-        self._check(self.lib.fe_set_params(self.ctx, ctypes.byref(cp)))
-        self.params = params
-
-    def load_reads(self, rs) -> None:
-        bases = np.ascontiguousarray(rs.bases, dtype=np.uint8)
-        offs = np.ascontiguousarray(rs.offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(rs.lengths, dtype=np.uint32)
-        self._check(self.lib.fe_load_reads(self.ctx, rs.first_iid, rs.nreads, bases.ctypes.data,
-                                           offs.ctypes.data, lens.ctypes.data))
-
-    def load_reads_device(self, first_iid: int, d_bases: int, d_offsets: int,
-                          lengths: np.ndarray) -> None:
-        """Reads already in HBM (device pointers, e.g. the buffers another stage loaded)."""
-        lens = np.ascontiguousarray(lengths, dtype=np.uint32)
-        self._check(self.lib.fe_load_reads_device(self.ctx, first_iid, lens.shape[0], d_bases,
-                                                  d_offsets, lens.ctypes.data))
+        super().__init__(load_library(), params, device)
 
     def run(self, overlaps: np.ndarray, bgn_id: int, end_id: int) -> np.ndarray:
         """findErrors -R bgn_id end_id over these overlaps -> the .red records (RED_DTYPE)."""
@@ -232,11 +166,6 @@ class FindErrors:
 
     def write_red(self, path: str) -> None:
         self._check(self.lib.fe_write_red(self.ctx, os.fsencode(path)))
-
-    def stats(self) -> dict:
-        s = _Stats()
-        self._check(self.lib.fe_get_stats(self.ctx, ctypes.byref(s)))
-        return {n: getattr(s, n) for n, _ in _Stats._fields_}
 
     def counters(self) -> dict:
         s = self.stats()

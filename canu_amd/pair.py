@@ -14,10 +14,11 @@ import os
 
 import numpy as np
 
+from . import _capi
+from ._capi import _atof, _atoi
 from .overlap_in_core import RECORD_DTYPE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "lib", "libcanu_pair.so")
+LIB_PATH = _capi.lib_path("pair")
 
 PAIR_STATUS = {0: "PAIR_OK", -1: "PAIR_ERR_NO_DEVICE", -2: "PAIR_ERR_BAD_PARAM",
                -3: "PAIR_ERR_UNSUPPORTED", -4: "PAIR_ERR_BAD_INPUT", -5: "PAIR_ERR_HIP",
@@ -28,10 +29,8 @@ LDS_COLUMNS = 16384                     # PAIR_LDS_COLUMNS
 STRIPE_ROWS = 4096                      # PAIR_STRIPE_ROWS
 
 
-class PairError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"{PAIR_STATUS.get(code, code)}: {msg}")
-        self.code = code
+class PairError(_capi.CapiError):
+    STATUS = PAIR_STATUS
 
 
 class _Params(ctypes.Structure):
@@ -60,24 +59,8 @@ def load_library(path: str | None = None):
     if _lib is not None:
         return _lib
     path = path or os.environ.get("CANU_PAIR_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise PairError(-1, f"{path} missing: run __graft_entry__.build()")
-    lib = ctypes.CDLL(path)
-    if lib.pair_abi_version() != ABI_VERSION:
-        raise PairError(-1, f"{path} has ABI {lib.pair_abi_version()}, this binding expects "
-                            f"{ABI_VERSION}: rebuild with __graft_entry__.build()")
-    P, V, U32, U64 = ctypes.POINTER, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    lib.pair_params_init.argtypes = [P(_Params)]
-    lib.pair_params_init.restype = None
-    lib.pair_last_error.restype = ctypes.c_char_p
-    lib.pair_ctx_create.argtypes = [P(_Params), ctypes.c_int, P(V)]
-    lib.pair_ctx_destroy.argtypes = [V]
-    lib.pair_ctx_destroy.restype = None
-    lib.pair_set_params.argtypes = [V, P(_Params)]
-    lib.pair_load_reads.argtypes = [V, U32, U32, V, V, V]
-    lib.pair_load_reads_device.argtypes = [V, U32, U32, V, V, V]
-    lib.pair_realign.argtypes = [V, V, U64, V]
-    lib.pair_get_stats.argtypes = [V, P(_Stats)]
+    lib = _capi.load("pair", path, ABI_VERSION, PairError, _Params, _Stats)
+    lib.pair_realign.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
     _lib = lib
     return lib
 
@@ -106,16 +89,6 @@ def parse_overlapPair_args(argv: list[str]) -> tuple[PairParameters, dict]:
     takes = {"-G": "gkp", "-O": "ovl", "-o": "out", "-b": "bgn", "-e": "end", "-t": "threads",
              "-memory": "memory"}
 
-    def atoi(s: str) -> int:
-        import re
-        m = re.match(r"\s*[+-]?\d+", s)
-        return int(m.group(0)) if m else 0
-
-    def atof(s: str) -> float:
-        import re
-        m = re.match(r"\s*[+-]?(\d+\.?\d*([eE][+-]?\d+)?|\.\d+([eE][+-]?\d+)?)", s)
-        return float(m.group(0)) if m else 0.0
-
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -127,11 +100,11 @@ def parse_overlapPair_args(argv: list[str]) -> tuple[PairParameters, dict]:
             if a in ("-G", "-O", "-o"):
                 job[takes[a]] = v
             elif a == "-erate":
-                P.max_erate = atof(v)
+                P.max_erate = _atof(v)
             elif a == "-len":
-                P.min_overlap_length = atoi(v)
+                P.min_overlap_length = _atoi(v)
             else:
-                job[takes[a]] = atoi(v)
+                job[takes[a]] = _atoi(v)
         elif a == "-partial":
             P.partial = True
         elif a == "-invert":
@@ -145,52 +118,12 @@ def parse_overlapPair_args(argv: list[str]) -> tuple[PairParameters, dict]:
     return P, job
 
 
-class OverlapPair:
+class OverlapPair(_capi.Context):
     """One overlapPair job on one gfx950 device: load reads, realign batches of overlaps."""
+    PREFIX, ERROR, PARAMS, STATS = "pair", PairError, PairParameters, _Stats
 
     def __init__(self, params: PairParameters | None = None, device: int = 0):
-        self.lib = load_library()
-        self.params = params or PairParameters()
-        self.ctx = None
-        ctx = ctypes.c_void_p()
-        cp = self.params.to_c()
-        self._check(self.lib.pair_ctx_create(ctypes.byref(cp), device, ctypes.byref(ctx)))
-        self.ctx = ctx
-
-    def _check(self, rc: int):
-        if rc != 0:
-            raise PairError(rc, self.lib.pair_last_error().decode())
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.pair_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, params: PairParameters) -> None:
-        cp = params.to_c()
-        self._check(self.lib.pair_set_params(self.ctx, ctypes.byref(cp)))
-        self.params = params
-
-    def load_reads(self, rs) -> None:
-        bases = np.ascontiguousarray(rs.bases, dtype=np.uint8)
-        offs = np.ascontiguousarray(rs.offsets, dtype=np.uint64)
-        lens = np.ascontiguousarray(rs.lengths, dtype=np.uint32)
-        self._check(self.lib.pair_load_reads(self.ctx, rs.first_iid, rs.nreads,
-                                             bases.ctypes.data, offs.ctypes.data,
-                                             lens.ctypes.data))
-
-    def load_reads_device(self, first_iid: int, d_bases: int, d_offsets: int,
-                          lengths: np.ndarray) -> None:
-        """Reads already in HBM (device pointers, e.g. the buffers another stage loaded)."""
-        lens = np.ascontiguousarray(lengths, dtype=np.uint32)
-        self._check(self.lib.pair_load_reads_device(self.ctx, first_iid, lens.shape[0],
-                                                    d_bases, d_offsets, lens.ctypes.data))
+        super().__init__(load_library(), params, device)
 
     def realign(self, records: np.ndarray) -> np.ndarray:
         """recomputeOverlaps over the records, in their order."""
@@ -199,11 +132,6 @@ class OverlapPair:
         self._check(self.lib.pair_realign(self.ctx, rec.ctypes.data if rec.size else None,
                                           rec.shape[0], out.ctypes.data if rec.size else None))
         return out
-
-    def stats(self) -> dict:
-        s = _Stats()
-        self._check(self.lib.pair_get_stats(self.ctx, ctypes.byref(s)))
-        return {n: getattr(s, n) for n, _ in _Stats._fields_}
 
     def counters(self) -> dict:
         """The counters under alignStats' names (overlapPair.C:158-175)."""

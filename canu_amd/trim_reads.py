@@ -17,11 +17,12 @@ import struct
 
 import numpy as np
 
-from .find_errors import _atof, _atoi, store_view  # noqa: F401  (store_view: the chain's middle)
+from . import _capi
+from ._capi import _atof, _atoi
+from .find_errors import store_view  # noqa: F401  (the chain's middle)
 from .overlap_in_core import RECORD_DTYPE
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(HERE, "lib", "libcanu_tr.so")
+LIB_PATH = _capi.lib_path("tr")
 
 TR_STATUS = {0: "TR_OK", -1: "TR_ERR_NO_DEVICE", -2: "TR_ERR_BAD_PARAM", -3: "TR_ERR_UNSUPPORTED",
              -4: "TR_ERR_BAD_INPUT", -5: "TR_ERR_HIP", -6: "TR_ERR_OOM", -7: "TR_ERR_STATE"}
@@ -39,10 +40,8 @@ COUNTERS = ("reads_in", "deleted_in", "no_trim_in", "reads_out", "no_ovl_out", "
 LOG_HEADER = "id\tinitL\tinitR\tfinalL\tfinalR\tmessage (DEL=deleted NOC=no change MOD=modified)\n"
 
 
-class TrError(RuntimeError):
-    def __init__(self, code: int, msg: str):
-        super().__init__(f"{TR_STATUS.get(code, code)}: {msg}")
-        self.code = code
+class TrError(_capi.CapiError):
+    STATUS = TR_STATUS
 
 
 class _Params(ctypes.Structure):
@@ -79,23 +78,11 @@ def load_library(path: str | None = None):
     if _lib is not None:
         return _lib
     path = path or os.environ.get("CANU_TR_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise TrError(-1, f"{path} missing: run __graft_entry__.build()")
-    lib = ctypes.CDLL(path)
-    if lib.tr_abi_version() != ABI_VERSION:
-        raise TrError(-1, f"{path} has ABI {lib.tr_abi_version()}, this binding expects "
-                          f"{ABI_VERSION}: rebuild with __graft_entry__.build()")
-    P, V, U32, U64 = ctypes.POINTER, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-    lib.tr_params_init.argtypes = [P(_Params)]
-    lib.tr_params_init.restype = None
-    lib.tr_last_error.restype = ctypes.c_char_p
+    lib = _capi.load("tr", path, ABI_VERSION, TrError, _Params, _Stats, reads=False)
+    V, U32 = ctypes.c_void_p, ctypes.c_uint32
     lib.tr_wave_capacity.restype = U32
-    lib.tr_ctx_create.argtypes = [P(_Params), ctypes.c_int, P(V)]
-    lib.tr_ctx_destroy.argtypes = [V]
-    lib.tr_ctx_destroy.restype = None
-    lib.tr_set_params.argtypes = [V, P(_Params)]
-    lib.tr_trim_reads.argtypes = [V, U32, V, V, V, U64, ctypes.c_int, U32, U32, P(_Result)]
-    lib.tr_get_stats.argtypes = [V, P(_Stats)]
+    lib.tr_trim_reads.argtypes = [V, U32, V, V, V, ctypes.c_uint64, ctypes.c_int, U32, U32,
+                                  ctypes.POINTER(_Result)]
     _lib = lib
     return lib
 
@@ -298,37 +285,12 @@ class TrimResult:
             f.write(self.stats_text())
 
 
-class TrimReads:
-    """One trimReads job on one gfx950 device."""
+class TrimReads(_capi.Context):
+    """One trimReads job on one gfx950 device.  It has no reads to load."""
+    PREFIX, ERROR, PARAMS, STATS = "tr", TrError, TrParameters, _Stats
 
     def __init__(self, params: TrParameters | None = None, device: int = 0):
-        self.lib = load_library()
-        self.params = params or TrParameters()
-        self.ctx = None
-        ctx = ctypes.c_void_p()
-        cp = self.params.to_c()
-        self._check(self.lib.tr_ctx_create(ctypes.byref(cp), device, ctypes.byref(ctx)))
-        self.ctx = ctx
-
-    def _check(self, rc: int):
-        if rc != 0:
-            raise TrError(rc, self.lib.tr_last_error().decode())
-
-    def close(self):
-        if getattr(self, "ctx", None):
-            self.lib.tr_ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_params(self, params: TrParameters) -> None:
-        cp = params.to_c()
-        self._check(self.lib.tr_set_params(self.ctx, ctypes.byref(cp)))
-        self.params = params
+        super().__init__(load_library(), params, device)
 
     def run(self, read_lengths, records, rules=1, id_range=None, device_records: int | None = None,
             n_device_records: int = 0) -> TrimResult:
@@ -352,8 +314,7 @@ class TrimReads:
         self._check(self.lib.tr_trim_reads(self.ctx, n, lens.ctypes.data, rl.ctypes.data, ptr, cnt,
                                            on_dev, id_min & U32_MAX, id_max & U32_MAX,
                                            ctypes.byref(res)))
-        s = _Stats()
-        self._check(self.lib.tr_get_stats(self.ctx, ctypes.byref(s)))
+        s = self._stats()
         counters = {k: (getattr(s, k).reads, getattr(s, k).bases) for k in COUNTERS}
         stats = {k: getattr(s, k) for k, t in _Stats._fields_ if t is not _Count}
         return TrimResult(params=dataclasses.replace(self.params), lengths=lens, counters=counters,

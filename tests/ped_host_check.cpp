@@ -6,6 +6,11 @@
 //   ped_host_check sizes <per_error> <limit> [<limit> ...]   a line per limit: rows worst first,
 //                                                           the regrown cap from `first` and
 //                                                           from `worst`, ROW_LOG_MAX
+//   ped_host_check launch <n_cu> <log_cap> <limit> <extra> <todo> [...]
+//                                                           a line per quadruple: ok, per_wave,
+//                                                           nwaves, blocks, scratch_bytes of
+//                                                           launch_size, WAVES_PER_BLOCK,
+//                                                           SCRATCH_BUDGET
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,7 +41,20 @@ int main(int argc, char **argv) {
     }
     return 0;
   }
+  if (argc >= 7 && (argc - 3) % 4 == 0 && !strcmp(argv[1], "launch")) {
+    const int n_cu = atoi(argv[2]);
+    for (int a = 3; a < argc; a += 4) {
+      const ped::LaunchSize L = ped::launch_size(strtoull(argv[a], nullptr, 10), atoi(argv[a + 1]),
+                                                 strtoull(argv[a + 2], nullptr, 10),
+                                                 strtoull(argv[a + 3], nullptr, 10), n_cu);
+      printf("%d %llu %llu %u %llu %d %llu\n", L.ok ? 1 : 0, (unsigned long long)L.per_wave,
+             (unsigned long long)L.nwaves, L.blocks, (unsigned long long)L.scratch_bytes,
+             ped::WAVES_PER_BLOCK, (unsigned long long)ped::SCRATCH_BUDGET);
+    }
+    return 0;
+  }
   fprintf(stderr, "usage: ped_host_check limit <erate> <max_errors> <upto> [...] | "
-                  "sizes <per_error> <limit> [...]\n");
+                  "sizes <per_error> <limit> [...] | launch <n_cu> <log_cap> <limit> <extra> <todo> "
+                  "[...]\n");
   return 1;
 }

@@ -494,3 +494,44 @@ def test_executable_equals_reference(built, tmp_path):
     cp = subprocess.run([exe, "-G", gkp, "-O", empty, "-R", "1", "2", "-c", str(tmp_path / "absent"),
                          "-o", out], capture_output=True, text=True, timeout=120)
     assert cp.returncode == 1 and "can't open" in cp.stderr
+
+
+def _crowd(n, seed):
+    """n overlaps among eight reads of about 48 bases of one 64-base stretch, in both
+    orientations: every ordered pair of reads, over and over."""
+    rng = np.random.default_rng(seed)
+    g = _rand(rng, 64)
+    reads, where = [], []
+    for _ in range(8):
+        L = int(rng.integers(44, 53))
+        s = int(rng.integers(0, len(g) - L + 1))
+        fl = int(rng.integers(0, 2)) if where else 0
+        r = _mutate(rng, g[s:s + L], 0.02)
+        reads.append(_rc(r) if fl else r)
+        where.append((s, s + L, fl))
+    assert {fl for _, _, fl in where} == {0, 1}
+    pairs = []
+    for a in range(8):
+        for b in range(8):
+            if a == b:
+                continue
+            (sa, ea, fa), (sb, eb, fb) = where[a], where[b]
+            ah = (sb - sa) if fa == 0 else (ea - eb)
+            bh = (eb - ea) if fa == 0 else (sa - sb)
+            ah = min(max(ah, -(len(reads[b]) - 1)), len(reads[a]) - 1)
+            pairs.append(FR.make_record(a + 1, b + 1, ah, bh, fa != fb))
+    return reads, [pairs[k % len(pairs)] for k in range(n)]
+
+
+def test_more_overlaps_than_waves(built):
+    """More overlaps than the grid has waves (eight per SIMD): the grid bound decides the number
+    of waves and every wave takes several overlaps off the work counter.  Two reads carry a
+    correction, so hangs are adjusted on the way."""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    reads, recs = _crowd(n_cu * 32 + 7, 57)
+    red = _red(len(reads), {2: [(20, FR.DELETE)], 5: [(10, FR.A_INSERT), (30, FR.C_SUBST)]})
+    gs, st, _, got = _check(reads, recs, red, 1, len(reads), 0.06)
+    assert gs["total"] == len(recs) == n_cu * 32 + 7
+    assert gs["regrows"] == 0 and gs["rows"] == st["rows"]
+    assert gs["total"] - gs["failed_either"] > len(recs) // 2

@@ -459,3 +459,42 @@ def test_executable_equals_reference(built, tmp_path):
     cp = subprocess.run([exe, "-G", gkp, "-O", str(tmp_path / "absent"), "-R", "1", "2", "-o", out],
                         capture_output=True, text=True, timeout=120)
     assert cp.returncode == 1 and "not an overlap store" in cp.stderr
+
+
+def _crowd(n, seed):
+    """n overlaps among eight reads of about 48 bases of one 64-base stretch, in both
+    orientations: every ordered pair of reads, over and over."""
+    rng = np.random.default_rng(seed)
+    g = _rand(rng, 64)
+    reads, where = [], []
+    for _ in range(8):
+        L = int(rng.integers(44, 53))
+        s = int(rng.integers(0, len(g) - L + 1))
+        fl = int(rng.integers(0, 2)) if where else 0
+        r = _mutate(rng, g[s:s + L], 0.02)
+        reads.append(_rc(r) if fl else r)
+        where.append((s, s + L, fl))
+    assert {fl for _, _, fl in where} == {0, 1}
+    pairs = []
+    for a in range(8):
+        for b in range(8):
+            if a == b:
+                continue
+            (sa, ea, fa), (sb, eb, fb) = where[a], where[b]
+            ah = (sb - sa) if fa == 0 else (ea - eb)
+            bh = (eb - ea) if fa == 0 else (sa - sb)
+            ah = min(max(ah, -(len(reads[b]) - 1)), len(reads[a]) - 1)
+            pairs.append(FR.make_record(a + 1, b + 1, ah, bh, fa != fb))
+    return reads, [pairs[k % len(pairs)] for k in range(n)]
+
+
+def test_more_overlaps_than_waves(built):
+    """More overlaps than the grid has waves (eight per SIMD): the grid bound decides the number
+    of waves and every wave takes several overlaps off the work counter."""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    reads, recs = _crowd(n_cu * 32 + 7, 57)
+    gs, st = _check(reads, recs, 1, len(reads), FR.defaults())
+    assert gs["n_passed"] + gs["n_failed"] == len(recs) == n_cu * 32 + 7
+    assert gs["regrows"] == 0 and gs["rows"] == st["rows"]
+    assert gs["n_passed"] > len(recs) // 2

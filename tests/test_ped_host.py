@@ -73,3 +73,48 @@ def test_row_log_sizes(host_check):
     by = dict(zip(limits, got))
     assert by[0][2] == 64 and by[1][2] == 4 + 64             # at 1 the worst case is the smaller
     assert by[cross - 1][2] == by[cross - 1][1] and by[cross][2] == PER_ERROR * cross + 64 < by[cross][1]
+
+
+N_CU = 256
+WAVES_PER_BLOCK = 4
+SCRATCH_BUDGET = 16 << 30
+ROW_LOG_MAX = 0x7fff0000
+EXTRA = {"findErrors": lambda limit: 2 * (limit + 8), "correctOverlaps": lambda limit: 0}
+
+
+def _launch(log_cap, limit, extra, todo):
+    """launch_size, restated: (per_wave, nwaves, blocks, scratch_bytes)."""
+    per_wave = log_cap + 3 * (limit + 2) + 2 * (limit + 4) + extra + 8
+    fit = max(1, SCRATCH_BUDGET // (per_wave * 4))
+    nwaves = min(todo, N_CU * 8 * WAVES_PER_BLOCK, fit)
+    return per_wave, nwaves, -(-nwaves // WAVES_PER_BLOCK), per_wave * nwaves * 4
+
+
+@pytest.mark.parametrize("stage", sorted(EXTRA))
+def test_launch_sizes(host_check, stage):
+    """A launch's scratch per wave, waves, blocks and bytes for both stages' extra ints: one
+    overlap, one overlap more than the grid holds, where the budget takes over from the grid, and
+    the first log that the 32-bit offsets refuse."""
+    extra = EXTRA[stage]
+    worst = lambda l: (l + 1) ** 2 + 64                        # noqa: E731
+    grid = N_CU * 8 * WAVES_PER_BLOCK
+    many = 4 * grid
+    budget = next(l for l in range(1, 1 << 20)
+                  if SCRATCH_BUDGET // (_launch(worst(l), l, extra(l), many)[0] * 4) < grid)
+    refused = next(l for l in range(46000, 1 << 20) if worst(l) > ROW_LOG_MAX)
+    assert 700 < budget < 740 and worst(refused - 1) <= ROW_LOG_MAX
+    cases = [(PER_ERROR * 3 + 64, 3, 1), (PER_ERROR * 3 + 64, 3, grid + 1),
+             (worst(budget - 1), budget - 1, many), (worst(budget), budget, many),
+             (worst(refused - 1), refused - 1, many), (worst(refused), refused, many)]
+    got = _lines(host_check, "launch", N_CU, *[v for c, l, t in cases for v in (c, l, extra(l), t)])
+    assert len(got) == len(cases)
+    for (log_cap, limit, todo), (ok, *sized, wpb, bud) in zip(cases, got):
+        assert (wpb, bud) == (WAVES_PER_BLOCK, SCRATCH_BUDGET)
+        if limit == refused:
+            assert ok == 0 and sized == [0, 0, 0, 0]           # refused, not sized
+        else:
+            assert ok == 1 and tuple(sized) == _launch(log_cap, limit, extra(limit), todo), (limit, todo)
+    assert got[0][2:4] == [1, 1]                               # one overlap: one wave, one block
+    assert got[1][2:4] == [grid, grid // WAVES_PER_BLOCK]      # the grid decides
+    assert got[2][2] == grid and got[3][2] < grid              # then the budget does
+    assert 1 <= got[4][2] < 4                                  # the largest log still gets a wave
