@@ -11,7 +11,9 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "lib")
 OUT = os.path.join(OUT_DIR, "libcanu_ovl.so")
 SOURCES = ["ovl_api.hip", "ovl_index.hip", "ovl_seed.hip", "ovl_extend.hip", "ovl_common.h",
-           "ovl_ovb.h", "ovl_plan.h", "ped_host.h"]
+           "ovl_ovb.h", "ovl_plan.h", "ped_host.h",
+           # the host side, included by ovl_api.hip
+           "ovl_ctx.h", "ovl_sq.hip", "ovl_build.hip", "ovl_find.hip", "ovl_driver.hip"]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                # doubles in the extension (branch score, slope, quality) must round exactly

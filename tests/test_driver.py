@@ -297,7 +297,7 @@ def test_gpu_driver_library_filters(built):
 @pytest.mark.parametrize("mode", ["0", "1"])
 def test_gpu_bloom_filter_is_exact(built, monkeypatch, mode):
     """The probe's Bloom filter (OverlapDriver batches probed mostly by reads outside the
-    hash range; ensure_bloom / use_bloom in ovl_api.hip) has no false negatives, so records
+    hash range; use_bloom in ovl_find.hip) has no false negatives, so records
     and every -s counter are those of the table alone: the production-batch job of
     10 kb reads in 70-read hash batches with the filter forced off (OVL_BLOOM=0) and on
     for every search (OVL_BLOOM=1, also the searches it would skip) against the oracle."""

@@ -1,5 +1,5 @@
 """The sorted query windows of OverlapDriver jobs (k_sq_keys / k_probe_sorted, sq_prepare in
-ovl_api.hip) against two failure modes that would lose or invent probe records:
+ovl_sq.hip) against two failure modes that would lose or invent probe records:
 
 * stale window slots: a reverse unit whose strand holds a NUL (the reverse complement of an
   'n') has fewer windows than the L - k + 1 slots its run reserves; those tail slots must be

@@ -169,8 +169,10 @@ def test_c4_full_plan_covers_the_reads(monkeypatch):
 def test_search_plan_header_under_sanitizers(tmp_path):
     """tests/ovl_plan_check.cpp, a program of its own: the search's batch arithmetic
     (canu_amd/csrc/ovl_plan.h -- the query-read rule, the budget cut, a chain launch's units,
-    live list and capacities, also after a budget halving) against hand-computed values,
-    under AddressSanitizer and UBSan."""
+    live list and capacities, also after a budget halving) and the driver's (the hash-read
+    rule, the ref schedule, a hash batch's stops, prefix and load cut, super-batch packing, the
+    search order, the query-chunk cut, the sorted windows' run layout, the index and table
+    shapes) against hand-computed values, under AddressSanitizer and UBSan."""
     import os
     import shutil
     import subprocess

@@ -5,7 +5,7 @@ targets in String_Olap_Space order; past the limit it sorts them by average diag
 walks the non-negative ones up while A_Olaps_For_Frag < limit, then the negative ones down
 while B_Olaps_For_Frag < limit, and Process_Matches (:481-487) stops extending matches off
 an end that has its limit.  Results depend on the order, so the GPU runs each query strand's
-pairs one after another in that order (k_extend's ORD variant, ovl_api.hip k_olim_*).
+pairs one after another in that order (k_extend's ORD variant, ovl_find.hip k_olim_*).
 
 CPU tests pin the oracle (oracle/oic_oracle.c) to the reference overlapInCore built from
 its sources (records and the -s counters); GPU tests hold the library to the oracle.
