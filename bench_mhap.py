@@ -67,9 +67,13 @@ def workload_key(args) -> dict:
 def mhap_source_hash() -> str:
     import hashlib
     h = hashlib.sha256()
-    for rel in ("canu_amd/csrc/mhap.hip", "include/canu_mhap.h"):
-        with open(os.path.join(ROOT, rel), "rb") as f:
-            h.update(rel.encode() + b"\0" + f.read())
+    csrc = os.path.join(ROOT, "canu_amd", "csrc")
+    for name in sorted(os.listdir(csrc)):
+        if name.startswith("mhap") and (name.endswith(".hip") or name.endswith(".h")):
+            with open(os.path.join(csrc, name), "rb") as f:
+                h.update(name.encode() + b"\0" + f.read())
+    with open(os.path.join(ROOT, "include", "canu_mhap.h"), "rb") as f:
+        h.update(b"include/canu_mhap.h\0" + f.read())
     return h.hexdigest()[:16]
 
 

@@ -74,8 +74,12 @@ PROF_OUT = os.path.join(OUT_DIR, "libcanu_ovl_prof.so")
 CLI_OUT = os.path.join(BIN_DIR, "overlapInCore")
 CLI_DEPS = _csrc("oic_main.cpp", "gkp_store.h") + _inc("canu_ovl.h")
 
+# the C-API scaffold of libcanu_mhap and the five libraries below meryl
+CAPI_DEPS = _csrc("capi_common.h", "hip_raii.h")
+
 MHAP_OUT = os.path.join(OUT_DIR, "libcanu_mhap.so")
-MHAP_DEPS = _csrc("mhap.hip") + _inc("canu_mhap.h")
+MHAP_DEPS = _csrc("mhap.hip", "mhap_hash.h", "mhap_common.h", "mhap_sketch.hip", "mhap_filter.hip",
+                  "mhap_host.h", "mhap_ctx.h") + CAPI_DEPS + _inc("canu_mhap.h", "canu_ovl.h")
 MHAP_CLI_OUT = os.path.join(BIN_DIR, "mhap")
 
 MERYL_OUT = os.path.join(OUT_DIR, "libcanu_meryl.so")
@@ -84,7 +88,6 @@ MERYL_CLI_OUT = os.path.join(BIN_DIR, "meryl")
 EMT_CLI_OUT = os.path.join(BIN_DIR, "estimate-mer-threshold")
 
 PAIR_OUT = os.path.join(OUT_DIR, "libcanu_pair.so")
-CAPI_DEPS = _csrc("capi_common.h", "hip_raii.h")   # the C-API scaffold of the five libraries below
 PAIR_DEPS = _csrc("pair.hip") + CAPI_DEPS + _inc("canu_pair.h", "canu_ovl.h")
 PAIR_CLI_OUT = os.path.join(BIN_DIR, "overlapPair")
 

@@ -1,5 +1,6 @@
-// capi_common.h -- what the C APIs of fe.hip, co.hip, pair.hip, fs.hip and tr.hip share: the last
-// error of a thread, HIP_TRY, the opening of a gfx950 device and the staging of host reads.
+// capi_common.h -- what the C APIs of fe.hip, co.hip, pair.hip, fs.hip, tr.hip and mhap.hip
+// share: the last error of a thread, HIP_TRY, the opening of a gfx950 device and the staging of
+// host reads.
 // Each of them is one translation unit of a library of its own, so all of it is inline.
 #pragma once
 
@@ -54,8 +55,9 @@ struct Device {              // a context derives from it
   hipStream_t stream = nullptr;
 };
 
-// Device `device` if it is a gfx950, made current, with a stream of the context's own.
-inline int open_device(int device, Device &d) {
+// Device `device` if it is a gfx950, made current, with a stream of the context's own
+// (stream_flags: hipStreamDefault, or hipStreamNonBlocking).
+inline int open_device(int device, Device &d, unsigned stream_flags = hipStreamDefault) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return fail(ERR_NO_DEVICE, "no HIP device %d", device);
@@ -65,7 +67,7 @@ inline int open_device(int device, Device &d) {
     return fail(ERR_NO_DEVICE, "device %d is %s, this library is built for gfx950", device,
                 prop.gcnArchName);
   HIP_TRY(hipSetDevice(device));
-  hipError_t e = hipStreamCreate(&d.stream);
+  hipError_t e = hipStreamCreateWithFlags(&d.stream, stream_flags);
   if (e != hipSuccess) return fail(ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(e));
   d.device = device;
   d.n_cu = prop.multiProcessorCount;
@@ -74,9 +76,9 @@ inline int open_device(int device, Device &d) {
 
 // *_ctx_create once the arguments are checked: a context on its device, with its parameters.
 template <class Ctx, class Params>
-int create_ctx(const Params *p, int device, Ctx **out) {
+int create_ctx(const Params *p, int device, Ctx **out, unsigned stream_flags = hipStreamDefault) {
   Ctx *c = new Ctx;
-  if (int rc = open_device(device, *c)) {
+  if (int rc = open_device(device, *c, stream_flags)) {
     delete c;
     return rc;
   }

@@ -20,6 +20,11 @@ struct DevBuf {
     bytes = std::max<size_t>(n, 1) * sizeof(T);
     return hipMalloc((void **)&p, bytes);
   }
+  // grow-only: an allocation that already holds n elements is kept, with its contents
+  hipError_t reserve(size_t n) {
+    if (p && n * sizeof(T) <= bytes) return hipSuccess;
+    return alloc(n);
+  }
 };
 
 struct Event {

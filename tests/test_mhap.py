@@ -236,7 +236,7 @@ def test_group_form_of_the_merge_equals_the_literal_merge():
 
 
 def test_bit_plane_draws_equal_the_xorshift_chain():
-    """The bit-sliced draws of k_mh_bitslice (mhap.hip), restated on the host: 32 chains in
+    """The bit-sliced draws of k_mh_bitslice (mhap_sketch.hip), restated on the host: 32 chains in
     64 planes (plane b, bit p = bit b of chain p), a xorshift64 step as plane XORs -- x ^= x <<
     21 is plane b ^= plane b - 21 from the top down, x ^= x >>> 35 plane b ^= plane b + 35 from
     the bottom up, x ^= x << 4 plane b ^= plane b - 4 from the top down -- equals the jar's
@@ -413,6 +413,23 @@ def test_gpu_matches_oracle(built, name):
     _same(got, want)
     assert st["overlaps"] == len(want) and st["candidates"] >= len(want)
     _same_rows(rows, M.sketch_rows(rs, P.as_oracle()))
+
+
+@pytest.mark.gpu
+def test_gpu_sketch_batches_match_oracle(built, small, small_oracle, monkeypatch):
+    """The MinHash batch loop through more than one batch: MHAP_KEY_BUDGET = 100,000 k-mers cuts
+    the "normal" case's 60 reads of 3 kb (120 strands of ~3 k k-mers each, ~360 k in all) into at
+    least three launches, whose sketch rows and records equal the restatement's."""
+    monkeypatch.setenv("MHAP_KEY_BUDGET", "100000")
+    P = mhap.MhapParameters()
+    m = mhap.Mhap(P, device=0)
+    got = m.run(small)
+    st = m.stats()
+    rows = _rows(m, small.nreads, P)
+    m.close()
+    assert st["sketch_launches"] >= 3
+    _same_rows(rows, M.sketch_rows(small, P.as_oracle()))
+    _same(got, small_oracle)
 
 
 def _freq_for(rs, every=11, span=2400):
