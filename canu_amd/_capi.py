@@ -1,5 +1,5 @@
-"""What the ctypes bindings of find_errors, correct_overlaps, pair, falconsense and trim_reads
-share: the loader of a libcanu_*.so, the error and context base classes, and C's atoi / atof."""
+"""What the ctypes bindings of find_errors, correct_overlaps, pair, falconsense, trim_reads and
+split_reads share: the loader of a libcanu_*.so, the error and context base classes, and C's atoi / atof."""
 from __future__ import annotations
 
 import ctypes

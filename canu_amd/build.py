@@ -109,6 +109,10 @@ TR_OUT = os.path.join(OUT_DIR, "libcanu_tr.so")
 TR_DEPS = _csrc("tr.hip") + CAPI_DEPS + _inc("canu_tr.h", "canu_ovl.h")
 TR_CLI_OUT = os.path.join(BIN_DIR, "trimReads")
 
+SR_OUT = os.path.join(OUT_DIR, "libcanu_sr.so")
+SR_DEPS = _csrc("sr.hip") + CAPI_DEPS + _inc("canu_sr.h", "canu_ovl.h")
+SR_CLI_OUT = os.path.join(BIN_DIR, "splitReads")
+
 
 def needs_build() -> bool:
     return _stale(OUT, OVL_DEPS)
@@ -216,11 +220,23 @@ def build_tr_cli(force: bool = False, verbose: bool = True) -> str:
                      _inc("canu_tr.h", "canu_ovl.h"), force, verbose)
 
 
+def build_sr(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_sr.so: splitReads, subread detection and read splitting."""
+    return _hipcc_lib(SR_OUT, "sr.hip", SR_DEPS, force, verbose)
+
+
+def build_sr_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/splitReads: the command line canu's trimming stage runs after trimReads."""
+    return _host_cli(SR_CLI_OUT, "sr_main.cpp", build_sr(verbose=verbose), "canu_sr",
+                     _csrc("gkp_store.h", "ovs_reader.h", "tr_files.h", "sr_files.h") +
+                     _inc("canu_sr.h", "canu_ovl.h"), force, verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
     build(force=force, profile="--profile" in sys.argv)
     if "--profile" not in sys.argv:
         for f in (build_mhap, build_cli, build_meryl, build_meryl_cli, build_emt_cli, build_pair,
                   build_pair_cli, build_fe, build_fe_cli, build_co, build_co_cli, build_fs,
-                  build_fs_cli, build_tr, build_tr_cli):
+                  build_fs_cli, build_tr, build_tr_cli, build_sr, build_sr_cli):
             f(force=force)
