@@ -113,6 +113,10 @@ SR_OUT = os.path.join(OUT_DIR, "libcanu_sr.so")
 SR_DEPS = _csrc("sr.hip") + CAPI_DEPS + _inc("canu_sr.h", "canu_ovl.h")
 SR_CLI_OUT = os.path.join(BIN_DIR, "splitReads")
 
+GFA_OUT = os.path.join(OUT_DIR, "libcanu_gfa.so")
+GFA_DEPS = _csrc("gfa.hip", "gfa_host.h") + CAPI_DEPS + _inc("canu_gfa.h")
+GFA_CLI_OUT = os.path.join(BIN_DIR, "alignGFA")
+
 
 def needs_build() -> bool:
     return _stale(OUT, OVL_DEPS)
@@ -232,11 +236,24 @@ def build_sr_cli(force: bool = False, verbose: bool = True) -> str:
                      _inc("canu_sr.h", "canu_ovl.h"), force, verbose)
 
 
+def build_gfa(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/lib/libcanu_gfa.so: alignGFA, graph links and unitig positions realigned."""
+    return _hipcc_lib(GFA_OUT, "gfa.hip", GFA_DEPS, force, verbose)
+
+
+def build_gfa_cli(force: bool = False, verbose: bool = True) -> str:
+    """canu_amd/bin/alignGFA: the command line canu runs on its graphs after consensus."""
+    return _host_cli(GFA_CLI_OUT, "gfa_main.cpp", build_gfa(verbose=verbose), "canu_gfa",
+                     _csrc("gfa_files.h", "gfa_host.h", "tgs_reader.h") + _inc("canu_gfa.h"),
+                     force, verbose)
+
+
 if __name__ == "__main__":
     force = "--force" in sys.argv
     build(force=force, profile="--profile" in sys.argv)
     if "--profile" not in sys.argv:
         for f in (build_mhap, build_cli, build_meryl, build_meryl_cli, build_emt_cli, build_pair,
                   build_pair_cli, build_fe, build_fe_cli, build_co, build_co_cli, build_fs,
-                  build_fs_cli, build_tr, build_tr_cli, build_sr, build_sr_cli):
+                  build_fs_cli, build_tr, build_tr_cli, build_sr, build_sr_cli, build_gfa,
+                  build_gfa_cli):
             f(force=force)
