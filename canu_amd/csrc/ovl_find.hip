@@ -358,7 +358,8 @@ struct ProbedBatch {
   uint32_t *uflags = nullptr;      // device: the units' flags
 };
 
-// the accumulator's flush thresholds (see FindRun::acc_append)
+// the accumulator's flush thresholds (see FindRun::acc_append); FindRun::acc_pairs is the
+// pairs' one, this its default
 static const uint64_t ACC_PAIRS = 4ull << 20, ACC_NODES = 1ull << 30;
 // per staged class: its work-queue cursor and its defer count in the extension's counters
 static const uint32_t ctr_next[4] = {5, 11, 13, 15}, ctr_defer[4] = {8, 12, 14, 10};
@@ -372,7 +373,12 @@ struct FindRun {
   // A batch is sized by seed hits (node pool + list-ordered copy: 32 B per hit); the probe
   // window budget adapts to the hits-per-window ratio seen so far (plan_chain)
   uint64_t hit_budget = 0, win_budget = 512ull << 20, win_cap = 1536ull << 20;
+  uint64_t win_floor = WIN_FLOOR;  // the window budget does not adapt or halve below this
   uint64_t per_unit = 256;         // pairs per unit the chain first allows
+  uint64_t acc_pairs = ACC_PAIRS;  // the accumulator is extended once it holds this many pairs
+  uint64_t out_first = 0;          // test knob: the output buffer's first room (0: the default)
+  uint32_t alloc_fails = 0;        // test knob: chain-buffer allocations still to count as failed
+  bool fake_oom = false;           // ... and whether that knob is set at all
   uint32_t chain_waves = 0;
   ExtPlan ext;
   uint64_t nout_ub = 0;            // records: an upper bound (<= 3 per pair) of the device counter
@@ -403,6 +409,25 @@ struct FindRun {
     hit_budget = std::max<uint64_t>(hit_budget, 16ull << 20);
     if (const char *e = getenv("OVL_TEST_PAIRS_PER_UNIT"))      // test knob: force the regrow path
       per_unit = std::max(1, atoi(e));
+    // test knobs: budgets far below the floors above, so that a job of a few hundred reads
+    // takes several probe batches, chain chunks, accumulator flushes and output regrows
+    // (tests/test_gpu_search_seams.py)
+    auto knob = [](const char *name, uint64_t *v) {
+      const char *e = getenv(name);
+      if (e) *v = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+      return e != nullptr;
+    };
+    knob("OVL_TEST_HIT_BUDGET", &hit_budget);                   // hits, no floor
+    if (knob("OVL_TEST_WIN_BUDGET", &win_budget)) {             // windows, no floor
+      win_cap = win_budget;
+      win_floor = 1;
+    }
+    knob("OVL_TEST_ACC_PAIRS", &acc_pairs);                     // the flush threshold
+    knob("OVL_TEST_OUT_RECORDS", &out_first);                   // records of room at the start
+    if (const char *e = getenv("OVL_TEST_CHAIN_ALLOC_FAILS")) { // force the halve-and-replan path
+      fake_oom = true;
+      alloc_fails = (uint32_t)std::max(0, atoi(e));
+    }
     chain_waves = 4u * OVL_CHAIN_OCC * c->n_cu;   // OVL_CHAIN_OCC blocks of 4 waves per CU
     if (fb.ctr.alloc(16) || fb.stats.alloc(16) || fb.xctr.alloc(16) || fb.xnout.alloc(1))
       return fail(OVL_ERR_OOM, "counters");
@@ -416,6 +441,7 @@ struct FindRun {
     HIPC(hipMemcpyAsync(fb.xnout.p, &nout32, 4, hipMemcpyHostToDevice, s));
     HIPC(hipStreamSynchronize(s));
     nout_ub = c->nout;
+    if (out_first) return ensure_out(c->nout + out_first);
     return ensure_out(std::max<uint64_t>(c->nout + (1u << 20), c->nout + nunits * 8));
   }
 
@@ -426,8 +452,10 @@ struct FindRun {
     HIPC(hipMemcpy(&cur, c->fb.xnout.p, 4, hipMemcpyDeviceToHost));
     DBuf<Rec> bigger;
     if (bigger.alloc(need + (need >> 2))) return fail(OVL_ERR_OOM, "output grow");
-    if (cur)
+    if (cur) {
       HIPC(hipMemcpyAsync(bigger.p, c->d_out.p, sizeof(Rec) * cur, hipMemcpyDeviceToDevice, s));
+      c->stats.out_regrows++;
+    }
     HIPC(hipStreamSynchronize(s));
     std::swap(bigger.p, c->d_out.p);
     std::swap(bigger.n, c->d_out.n);
@@ -666,6 +694,7 @@ struct FindRun {
   int flush_acc() {
     if (int rc = collect_extension()) return rc;
     auto &A = c->acc;
+    if (A.np) c->stats.acc_flushes++;
     int rc = launch_extension(A.units.p, A.pairs.p, A.pnodes.p, (uint32_t)A.np, (uint32_t)A.nu);
     A.nu = A.nn = A.np = 0;
     return rc;
@@ -685,7 +714,7 @@ struct FindRun {
     // accumulator holds is extended rather than moved into bigger buffers: a regrow on a full
     // device costs ~1 s (the full-size configs[4] job, r05e), while smaller launches lose to
     // their tails (one launch per search: extension 8.4 -> 23 s, r05f)
-    if (!acc_fits() && (A.np >= ACC_PAIRS / 4 || A.nn >= ACC_NODES / 4))
+    if (!acc_fits() && (A.np >= std::max<uint64_t>(1, acc_pairs / 4) || A.nn >= ACC_NODES / 4))
       if (int rc = flush_acc()) return rc;
     if (!acc_fits()) {
       // growing moves the buffers: the pending extension (which reads them) must be done,
@@ -738,7 +767,7 @@ struct FindRun {
       B->nb = take_within(uwin, u0, (uint32_t)units.size(), win_budget) - u0;
       const int rc = probe_batch(c, units.data() + u0, uwin.data() + u0, B->nb, bloom, &B->rbase);
       if (rc == OVL_OK) break;
-      if (rc != OVL_ERR_OOM || B->nb == 1 || win_budget <= (16ull << 20)) return rc;
+      if (rc != OVL_ERR_OOM || B->nb == 1 || win_budget <= win_floor) return rc;
       win_cap = win_budget = win_budget / 2;
     }
     const uint32_t nb = B->nb;
@@ -845,7 +874,14 @@ struct FindRun {
     const uint32_t hash_reads = c->hash_end_iid - c->hash_bgn_iid + 1;
     auto plan = [&]() {
       return plan_chain(B.uh.data(), B.nb, B.rbase.data(), hit_budget, per_unit, chain_waves,
-                        OVL_NODE_BLOCK, win_cap);
+                        OVL_NODE_BLOCK, win_cap, win_floor);
+    };
+    // OVL_TEST_CHAIN_ALLOC_FAILS: the first evaluations count as failed whatever the grows said
+    // (what they allocated is dropped below, as after a real failure)
+    auto grow_failed = [&](bool failed) {
+      if (!alloc_fails) return failed;
+      alloc_fails--;
+      return true;
     };
     ChainPlan P = plan();
     bool planned = true;               // P is new: its live list is not uploaded yet
@@ -855,11 +891,12 @@ struct FindRun {
         return fail(OVL_ERR_UNSUPPORTED, "chain buffers past 2^32 entries (%llu hits)",
                     (unsigned long long)P.hsum);
       // sized for the hit budget, not this batch's hits: the next batch reuses them as they are
-      if (fb.pool.grow(std::max(P.pool_cap, chain_pool_for(hit_budget, chain_waves, OVL_NODE_BLOCK))) ||
-          fb.pnodes.grow(std::max<uint64_t>(P.pnodes_cap, hit_budget + 1)) || fb.pairs.grow(P.pairs_cap) ||
-          fb.big.grow(P.nc) || fb.chits.grow(1)) {
-        if (P.nc == 1 || P.hsum <= (16ull << 20))
+      if (grow_failed(fb.pool.grow(std::max(P.pool_cap, chain_pool_for(hit_budget, chain_waves, OVL_NODE_BLOCK))) ||
+                      fb.pnodes.grow(std::max<uint64_t>(P.pnodes_cap, hit_budget + 1)) ||
+                      fb.pairs.grow(P.pairs_cap) || fb.big.grow(P.nc) || fb.chits.grow(1))) {
+        if (P.nc == 1 || P.hsum <= (fake_oom ? 1 : 16ull << 20))
           return fail(OVL_ERR_OOM, "chain buffers (%llu hits)", (unsigned long long)P.hsum);
+        c->stats.budget_halvings++;
         hit_budget = P.hsum / 2;                         // fewer units per chain launch
         // the buffers that did fit were sized for the larger budget: drop them too
         fb.pool.release();
@@ -958,6 +995,7 @@ struct FindRun {
       c->stats.chain_retries++;
     }
     win_budget = P.win_budget;
+    c->stats.chain_launches++;
     float t = 0;
     (void)hipEventElapsedTime(&t, c->ev[4], c->ev[5]);
     c->stats.ms_seed += t;
@@ -1099,7 +1137,7 @@ static int find_impl(ovl_ctx *c, uint32_t bgn, uint32_t end, uint32_t lib_lo, ui
     auto &fb = c->fb;
     if (!run.ordered) {
       if (int rc = run.acc_append(fb.units.p, nc, fb.pnodes.p, nnodes, fb.pairs.p, npairs)) return rc;
-      if (c->acc.np >= ACC_PAIRS || c->acc.nn >= ACC_NODES)
+      if (c->acc.np >= run.acc_pairs || c->acc.nn >= ACC_NODES)
         if (int rc = run.flush_acc()) return rc;
     } else {
       if (int rc = run.launch_extension(fb.units.p, fb.pairs.p, fb.pnodes.p, npairs, nc)) return rc;

@@ -80,14 +80,17 @@ struct ChainPlan {
 // adapts to the hits-per-window ratio seen, so that a batch's probe results are all consumed
 // (units beyond the hit budget would otherwise be re-probed).  Every value a chain launch needs
 // comes from one call: after a budget change, plan again and use all of the new plan.
+// win_floor: the fewest windows the next probe batch is given (below win_cap); the tests'
+// window-budget knob lowers it to 1.
+static const uint64_t WIN_FLOOR = 16ull << 20;
 inline ChainPlan plan_chain(const uint32_t *uh, uint32_t nb, const uint64_t *rbase,
                             uint64_t hit_budget, uint64_t per_unit, uint32_t chain_waves,
-                            uint32_t node_block, uint64_t win_cap) {
+                            uint32_t node_block, uint64_t win_cap, uint64_t win_floor = WIN_FLOOR) {
   ChainPlan P;
   P.nc = take_within(uh, 0, nb, hit_budget, &P.hsum);
   const double ratio = (double)P.hsum / (double)std::max<uint64_t>(1, rbase[P.nc]);
   const double wb = (double)hit_budget / std::max(ratio, 1e-3) * 1.05;
-  P.win_budget = (uint64_t)std::min(std::max(wb, 16.0 * (1 << 20)), (double)win_cap);
+  P.win_budget = (uint64_t)std::min(std::max(wb, (double)win_floor), (double)win_cap);
   P.live.reserve(P.nc);
   for (uint32_t i = 0; i < P.nc; i++)
     if (uh[i]) P.live.push_back(i);

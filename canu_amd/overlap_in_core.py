@@ -65,7 +65,9 @@ class _Stats(ctypes.Structure):
          ("long_stage_len", ctypes.c_uint32), ("seed_nodes", ctypes.c_uint64),
          ("probe_sorted_launches", ctypes.c_uint32), ("sq_resorted", ctypes.c_uint32),
          ("query_chunks", ctypes.c_uint32), ("super_batches", ctypes.c_uint32),
-         ("sq_declined", ctypes.c_uint32), ("find_releases", ctypes.c_uint32)]
+         ("sq_declined", ctypes.c_uint32), ("find_releases", ctypes.c_uint32),
+         ("chain_launches", ctypes.c_uint32), ("acc_flushes", ctypes.c_uint32),
+         ("out_regrows", ctypes.c_uint32), ("budget_halvings", ctypes.c_uint32)]
 
 
 class _IndexDesc(ctypes.Structure):
@@ -108,7 +110,7 @@ EXPORTS = ["ovl_params_init", "ovl_params_finalize", "ovl_ctx_create", "ovl_ctx_
 _lib = None
 
 
-ABI_VERSION = 8          # OVL_ABI_VERSION of include/canu_ovl.h
+ABI_VERSION = 9         # OVL_ABI_VERSION of include/canu_ovl.h
 
 
 def load_library(path: str | None = None):

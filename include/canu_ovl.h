@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define OVL_ABI_VERSION 8
+#define OVL_ABI_VERSION 9
 
 typedef enum {
   OVL_OK               =  0,
@@ -251,6 +251,13 @@ typedef struct {
   uint32_t find_releases;          /* search buffers released because an index build ran out
                                       of memory (the next search allocates them again; a
                                       chunk's sorted windows go with them; ABI 8) */
+  /* ABI 9: how often a search passed each seam between its steps (tests of the search's
+     batch, chunk and accumulator handling; 1 / 1 / 0 / 0 for a job that fits every budget) */
+  uint32_t chain_launches;         /* chain chunks: hit-budget cuts of the probed batches  */
+  uint32_t acc_flushes;            /* extensions of what the pair accumulator held         */
+  uint32_t out_regrows;            /* moves of the records held into a bigger buffer       */
+  uint32_t budget_halvings;        /* hit budgets halved because the chain buffers did not
+                                      fit, the batch planned again                         */
 } ovl_stats;
 
 int         ovl_get_stats(ovl_ctx *ctx, ovl_stats *out);

@@ -135,6 +135,27 @@ static void check_plan_chain() {
   CHECK(D.win_budget == 26250000);
   D = plan_chain(many, 2, rbase, 1000000000, 1, 4, 16, 20ull << 20);
   CHECK(D.win_budget == 20ull << 20);
+  // the floor as a parameter, at 1 (the tests' window-budget knob): 10000 / (8000 / 200) * 1.05
+  // = 262.5 windows, far below 16 M; a cap below that still binds; nothing else moves
+  ChainPlan F = plan_chain(many, 2, rbase, 10000, 1, 4, 16, 1ull << 30, 1);
+  CHECK(F.win_budget == 262);
+  CHECK(F.nc == 2 && F.hsum == 8000 && F.all_live() && F.pairs_cap == 1026 && F.pnodes_cap == 8001);
+  F = plan_chain(many, 2, rbase, 10000, 1, 4, 16, 100, 1);
+  CHECK(F.win_budget == 100);
+  F = plan_chain(many, 2, rbase, 1, 1, 4, 16, 100, 1);            // 1 / 40 * 1.05 < 1: the floor
+  CHECK(F.nc == 1 && F.win_budget == 1);
+  F = plan_chain(uh, 8, rbase, 24, 2, 4, 16, 1ull << 30, 1);      // case A: 840, give or take
+  CHECK(F.win_budget >= 839 && F.win_budget <= 840 && F.win_budget <= (1ull << 30));
+  // the default floor: the values as before (case A's 16 M, D's 26.25 M), named or left out
+  CHECK(WIN_FLOOR == 16ull << 20);
+  F = plan_chain(many, 2, rbase, 10000, 1, 4, 16, 1ull << 30);
+  CHECK(F.win_budget == 16ull << 20);
+  F = plan_chain(many, 2, rbase, 10000, 1, 4, 16, 1ull << 30, WIN_FLOOR);
+  CHECK(F.win_budget == 16ull << 20);
+  F = plan_chain(many, 2, rbase, 1000000000, 1, 4, 16, 1ull << 30, WIN_FLOOR);
+  CHECK(F.win_budget == 26250000);
+  F = plan_chain(many, 2, rbase, 10000, 1, 4, 16, 1ull << 20);    // a cap below the floor wins
+  CHECK(F.win_budget == 1ull << 20);
   // case B: no hits at all
   const uint32_t zero[4] = {0, 0, 0, 0};
   ChainPlan B = plan_chain(zero, 4, rbase, 10, 2, 4, 16, 1ull << 30);
