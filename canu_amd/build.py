@@ -87,8 +87,11 @@ MERYL_DEPS = _csrc("meryl.hip", "meryl_host.h") + _inc("canu_meryl.h")
 MERYL_CLI_OUT = os.path.join(BIN_DIR, "meryl")
 EMT_CLI_OUT = os.path.join(BIN_DIR, "estimate-mer-threshold")
 
+# the aligner pair.hip, fs.hip and gfa.hip share, and its host side
+EDLIB_DEPS = _csrc("edlib_wave.h", "edlib_host.h", "edlib_launch.h") + CAPI_DEPS
+
 PAIR_OUT = os.path.join(OUT_DIR, "libcanu_pair.so")
-PAIR_DEPS = _csrc("pair.hip") + CAPI_DEPS + _inc("canu_pair.h", "canu_ovl.h")
+PAIR_DEPS = _csrc("pair.hip") + EDLIB_DEPS + _inc("canu_pair.h", "canu_ovl.h")
 PAIR_CLI_OUT = os.path.join(BIN_DIR, "overlapPair")
 
 # the aligner fe.hip and co.hip share, and its host side
@@ -102,7 +105,7 @@ CO_DEPS = _csrc("co.hip") + PED_DEPS + _inc("canu_co.h", "canu_fe.h", "canu_ovl.
 CO_CLI_OUT = os.path.join(BIN_DIR, "correctOverlaps")
 
 FS_OUT = os.path.join(OUT_DIR, "libcanu_fs.so")
-FS_DEPS = _csrc("fs.hip", "fs_fasta.h") + CAPI_DEPS + _inc("canu_fs.h")
+FS_DEPS = _csrc("fs.hip", "fs_fasta.h") + EDLIB_DEPS + _inc("canu_fs.h")
 FS_CLI_OUT = os.path.join(BIN_DIR, "falconsense")
 
 TR_OUT = os.path.join(OUT_DIR, "libcanu_tr.so")
@@ -114,7 +117,7 @@ SR_DEPS = _csrc("sr.hip") + CAPI_DEPS + _inc("canu_sr.h", "canu_ovl.h")
 SR_CLI_OUT = os.path.join(BIN_DIR, "splitReads")
 
 GFA_OUT = os.path.join(OUT_DIR, "libcanu_gfa.so")
-GFA_DEPS = _csrc("gfa.hip", "gfa_host.h") + CAPI_DEPS + _inc("canu_gfa.h")
+GFA_DEPS = _csrc("gfa.hip", "gfa_host.h") + EDLIB_DEPS + _inc("canu_gfa.h")
 GFA_CLI_OUT = os.path.join(BIN_DIR, "alignGFA")
 
 

@@ -1,21 +1,12 @@
 // fs.hip -- libcanu_fs.so: canu's falconsense (src/correction/falconsense.C, falconConsensus*.C)
 // on gfx950.  include/canu_fs.h says what is reproduced; this is how.
 //
-//   k_fs_locate     one wave per evidence read: edlib's EDLIB_MODE_HW result in closed form.  An
-//                   infix pass gives the distance and the first best end column, a prefix pass
-//                   of the reversed query over the reversed target up to that column gives the
-//                   longest start; then the two rejection tests of alignReadsToTemplate.
-//   k_fs_path       one wave per surviving evidence read: obtainAlignment's recursion with an
-//                   explicit stack in LDS.  A split runs the left half and the reversed right
-//                   half, keeps Pv / Mv and the end score of every 64-row block of the two last
-//                   columns, and takes the first row r with L[r] + R[r+1] == best as a wave-wide
-//                   first match, then the two boundary rules.  A leaf keeps Pv / Mv / the block
-//                   score of every column -- under FS_LEAF_BYTES by the leaf rule, so the
-//                   scratch of a wave is fixed -- and walks up / left / diagonal from the
-//                   corner.  The leaf's operations (one byte each, backwards) go through a
-//                   per-wave buffer; tags are then made 64 operations at a time with ballots
-//                   and written with their place in (evidence, tag) order.  Alignment strings
-//                   are never made.
+//   k_fs_locate     one wave per evidence read: edlib's EDLIB_MODE_HW result (edlib_wave.h's
+//                   wave_locate), then the two rejection tests of alignReadsToTemplate.
+//   k_fs_path       one wave per surviving evidence read: obtainAlignment's recursion
+//                   (edlib_wave.h's wave_path, leaves under FS_LEAF_BYTES).  Its operations
+//                   become tags 64 at a time with ballots, written with their place in
+//                   (evidence, tag) order.  Alignment strings are never made.
 //   hipcub          a segmented radix sort of each template's tags by (t_pos, delta, base,
 //                   link); the sort is stable, so a run's first value is its first appearance.
 //   k_fs_consensus  one wave per template: coverage, links (runs) and columns (runs of runs),
@@ -28,9 +19,6 @@
 // vanishes in a sum with any nonzero multiple of 0.5, 0 + DBL_MIN is not greater than DBL_MIN,
 // so DBL_MIN is 0 here and "greater than DBL_MIN" is "greater than 0" (tests/test_fs_cpu.py
 // compares the two forms).
-//
-// The aligner core (dp_pass) is that of pair.hip: Myers' bit-vector recurrence, lane b holding
-// rows 64b..64b+63, columns as a skewed wavefront, 4096-row stripes.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -44,22 +32,23 @@
 
 #include "../../include/canu_fs.h"
 #include "capi_common.h"
+#include "edlib_launch.h"
 #include "fs_fasta.h"
 
 namespace {
 
 using capi::fail;
+using edw::LDS_WORDS;
+using edw::OP_DELETE;
+using edw::OP_INSERT;
+using edw::OP_MATCH;
+using edw::Span;
+using edw::STACK_DEPTH;
+using edw::uni;
+using edw::WAVES_PER_BLOCK;
 
 CAPI_SAME_CODES(FS);
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr int STRIPE_ROWS = 4096;                     // 64 lanes x 64 rows
-constexpr int LDS_COLUMNS = 16384;                    // stripe-boundary row kept in LDS
-constexpr int LDS_WORDS = LDS_COLUMNS / 16;           // 2 bits per column
-constexpr int LEAF_ENTRIES = FS_LEAF_BYTES / 20 + 1;  // block columns of a leaf
-constexpr int STACK_DEPTH = 40;                       // the target halves at every level
-constexpr uint32_t MAX_READLEN = (1u << 21) - 1;      // AS_MAX_READLEN
 
-enum : int { OP_MATCH = 0, OP_INSERT = 1, OP_DELETE = 2, OP_MISMATCH = 3 };   // EDLIB_EDOP_*
 // the base of a tag and of its predecessor: A C G T N - and '.', the first tag's predecessor
 enum : int { CH_N = 4, CH_GAP = 5, CH_NONE = 6 };
 
@@ -95,176 +84,7 @@ struct Tp {                  // one template of the batch
   int32_t len;
 };
 
-// ------------------------------------------------------------------ read encoding
-
-__global__ void k_fs_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
-                            const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ len,
-                            uint32_t nreads, uint8_t *__restrict__ fwd, uint8_t *__restrict__ rc,
-                            uint32_t *__restrict__ bad) {
-  for (uint32_t r = blockIdx.x; r < nreads; r += gridDim.x) {
-    const uint8_t *s = bases + src_off[r];
-    const uint64_t d = dst_off[r];
-    const uint32_t L = len[r];
-    for (uint32_t i = threadIdx.x; i < L; i += blockDim.x) {
-      const uint8_t ch = s[i];
-      uint8_t c = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
-      if (c == 4 && ch != 'N') atomicOr(bad, 1u);
-      fwd[d + i] = c;
-      rc[d + (L - 1 - i)] = c < 4 ? (uint8_t)(3 - c) : c;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ the aligner
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ int dpp_from_lower(int v, int lane0) {   // lane l <- v[l-1]
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xf, 0xf, false);
-}
-
-struct Seq {                 // a span of an oriented read, read forwards or backwards
-  const uint8_t *p;
-  int n;
-  int rev;                   // element i is p[n-1-i]
-  __device__ __forceinline__ int at(int i) const { return p[rev ? n - 1 - i : i]; }
-};
-
-struct PassOut {
-  int best, bestcol;         // minimum of the bottom row, the first column attaining it
-  int lastcol;               // last column whose bottom-row score == want (-1: none)
-  int fin;                   // bottom-row score at the last column
-};
-
-// What a pass leaves behind besides its bottom row.  Block g is rows 64g..64g+63.
-struct Keep {
-  uint64_t *colP, *colM;     // leaf: Pv / Mv of block g after column j at [g * n + j]
-  int *colS;                 //       and the score of the block's last row there
-  uint64_t *endP, *endM;     // split: Pv / Mv of block g after the last column at [g]
-  int *endS;                 //        and the score of the block's last row there
-};
-
-// Bottom row of the edit-distance matrix of q (rows) against t (columns); top_hin 0 lets an
-// alignment start at any column (infix), 1 charges every skipped target base (prefix, global).
-// Needs q.n >= 1, t.n >= 1.  Every lane of the wave is in, with the same arguments.
-__device__ PassOut dp_pass(const Seq q, const Seq t, const int top_hin, const int want,
-                           uint32_t *lrow, uint32_t *grow, const Keep keep) {
-  const int lane = threadIdx.x & 63;
-  const int m = q.n, n = t.n;
-  const int nstripes = (m + STRIPE_ROWS - 1) / STRIPE_ROWS;
-  const bool use_g = n > LDS_COLUMNS;
-  int best = INT_MAX, bestcol = -1, lastcol = -1, sc = m;
-  int lb = 0;
-  for (int st = 0; st < nstripes; st++) {
-    const int r0 = st * STRIPE_ROWS;
-    const int rows = min(STRIPE_ROWS, m - r0);
-    const int nb = (rows + 63) >> 6;
-    const bool last = st == nstripes - 1;
-    lb = nb - 1;
-    uint64_t pe0 = 0, pe1 = 0, pe2 = 0, pe3 = 0, pe4 = 0;
-    for (int c = 0; c < nb; c++) {
-      const int i = r0 + c * 64 + lane;
-      const int code = i < m ? q.at(i) : 7;
-      const uint64_t b0 = __ballot(code == 0), b1 = __ballot(code == 1),
-                     b2 = __ballot(code == 2), b3 = __ballot(code == 3),
-                     b4 = __ballot(code == 4);
-      if (lane == c) { pe0 = b0; pe1 = b1; pe2 = b2; pe3 = b3; pe4 = b4; }
-    }
-    uint64_t Pv = ~0ull, Mv = 0;
-    const bool trk = last && lane == lb;
-    // the last row of this lane's block, whose score the lane follows along the columns (the
-    // boundary column holds row + 1)
-    const int lrow_abs = min(r0 + 64 * (lane + 1), m) - 1;
-    const int rr = lane < nb ? (lrow_abs & 63) : 63;
-    sc = lrow_abs + 1;
-    const size_t gblk = (size_t)(st * 64 + lane);
-    int x = 1;                                  // (hout + 1) | base << 2, handed to lane + 1
-    uint32_t cur = lane < n ? (uint32_t)t.at(lane) : 4u;
-    uint32_t nxt = 64 + lane < n ? (uint32_t)t.at(64 + lane) : 4u;
-    uint32_t hw = 0, acc = 0;
-    const int nsteps = n + nb - 1;
-    for (int s = 0; s < nsteps; s++) {
-      if ((s & 63) == 0 && s > 0) {
-        cur = nxt;
-        const int c = s + 64 + lane;
-        nxt = c < n ? (uint32_t)t.at(c) : 4u;
-      }
-      const int base0 = __builtin_amdgcn_readlane((int)cur, s & 63);
-      int hin0 = top_hin;
-      if (st > 0) {
-        if ((s & 15) == 0 && s < n) hw = use_g ? grow[s >> 4] : lrow[s >> 4];
-        hin0 = (int)((hw >> (2 * (s & 15))) & 3u) - 1;
-      }
-      const int xin = dpp_from_lower(x, (hin0 + 1) | (base0 << 2));
-      const int j = s - lane;
-      const bool act = lane < nb && j >= 0 && j < n;
-      int d = 0;
-      if (act) {
-        const int hin = (xin & 3) - 1;
-        const int b = xin >> 2;
-        const uint64_t s0 = 0 - (uint64_t)(b & 1), s1 = 0 - (uint64_t)((b >> 1) & 1),
-                       s2 = 0 - (uint64_t)(b >> 2);
-        const uint64_t e01 = (pe0 & ~s0) | (pe1 & s0), e23 = (pe2 & ~s0) | (pe3 & s0);
-        const uint64_t e03 = (e01 & ~s1) | (e23 & s1);
-        uint64_t Eq = (e03 & ~s2) | (pe4 & s2);
-        const uint64_t neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
-        const uint64_t Xv = Eq | Mv;
-        Eq |= neg;
-        const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-        uint64_t Ph = Mv | ~(Xh | Pv);
-        uint64_t Mh = Pv & Xh;
-        d = (int)((Ph >> 63) & 1) - (int)((Mh >> 63) & 1);
-        sc += (int)((Ph >> rr) & 1) - (int)((Mh >> rr) & 1);
-        Ph = (Ph << 1) | pos;
-        Mh = (Mh << 1) | neg;
-        Pv = Mh | ~(Xv | Ph);
-        Mv = Ph & Xv;
-        if (trk) {
-          if (sc < best) { best = sc; bestcol = j; }
-          if (sc == want) lastcol = j;
-        }
-        if (keep.colP) {
-          const size_t at = gblk * (size_t)n + (size_t)j;
-          keep.colP[at] = Pv;
-          keep.colM[at] = Mv;
-          keep.colS[at] = sc;
-        }
-        if (!last && lane == lb) {              // lane 63: the next stripe's top boundary
-          acc |= (uint32_t)(d + 1) << (2 * (j & 15));
-          if ((j & 15) == 15 || j == n - 1) {
-            if (use_g) grow[j >> 4] = acc; else lrow[j >> 4] = acc;
-            acc = 0;
-          }
-        }
-      }
-      x = (d + 1) | (xin & ~3);
-    }
-    if (keep.endP && lane < nb) {
-      keep.endP[gblk] = Pv;
-      keep.endM[gblk] = Mv;
-      keep.endS[gblk] = sc;
-    }
-    if (!last) __threadfence();                 // lane 63's row is read by every lane next
-  }
-  PassOut o;
-  o.best = __shfl(best, lb);
-  o.bestcol = __shfl(bestcol, lb);
-  o.lastcol = __shfl(lastcol, lb);
-  o.fin = __shfl(sc, lb);
-  return o;
-}
-
-// Score of row r (0 <= r < m) from the block's end score and its Pv / Mv: the rows above the
-// block's last row down to r + 1 are taken back.
-__device__ __forceinline__ int row_score(const uint64_t P, const uint64_t M, const int end_score,
-                                         const int r, const int m) {
-  const int b = r >> 6;
-  const int lastbit = (min(64 * (b + 1), m) - 1) & 63;
-  const uint64_t upto = lastbit == 63 ? ~0ull : ((1ull << (lastbit + 1)) - 1);
-  const uint64_t above = (r & 63) == 63 ? 0ull : (~0ull << ((r & 63) + 1));
-  const uint64_t hi = above & upto;
-  return end_score - __popcll(P & hi) + __popcll(M & hi);
-}
+// ------------------------------------------------------------------ the location
 
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
 void k_fs_locate(const uint8_t *__restrict__ fwd, const uint8_t *__restrict__ rcs,
@@ -277,27 +97,21 @@ void k_fs_locate(const uint8_t *__restrict__ fwd, const uint8_t *__restrict__ rc
   const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;
   const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
   uint32_t *grow = scratch ? scratch + gw * scratch_words : nullptr;
-  const Keep none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   for (uint32_t e = (uint32_t)gw; e < n_ev; e += n_waves) {
     const Ev ev = evs[e];
     const int m = uni(ev.qlen), wb = uni(ev.wb), n = uni(ev.we) - wb;
     const uint8_t *qp = (uni((int)ev.rc) ? rcs : fwd) + ev.seq;
     const uint8_t *tp = fwd + tps[ev.tmpl].seq + wb;
-    const PassOut f = dp_pass(Seq{qp, m, 0}, Seq{tp, n, 0}, 0, INT_MIN, s_row[wave], grow, none);
-    unsigned long long c = (unsigned long long)m * n;
-    const int best = uni(f.best), end = uni(f.bestcol);
-    Loc o{best, 0, end, 0};
-    if (best <= uni(ev.tol)) {
-      // the last column of the reversed prefix pass still at `best` is the longest alignment
-      const PassOut r = dp_pass(Seq{qp, m, 1}, Seq{tp, end + 1, 1}, 1, best, s_row[wave], grow, none);
-      c += (unsigned long long)m * (end + 1);
-      o.start = end - uni(r.lastcol);
+    const edw::Located L = edw::wave_locate<5>(Span{qp, m}, Span{tp, n}, uni(ev.tol), true,
+                                               s_row[wave], grow);
+    Loc o{L.dist, L.start, L.end, 0};
+    if (L.ok) {
       // alignDiff = editDistance / (double)(end - start): one short of the span, as there
-      const double diff = (double)best / (double)(end - o.start);
+      const double diff = (double)L.dist / (double)(L.end - L.start);
       o.ok = diff >= max_difference ? 0 : 1;
     }
     loc[e] = o;
-    cells[e] = c;
+    cells[e] = L.cells;
   }
 }
 
@@ -366,42 +180,20 @@ __device__ void emit_tags(TagState &S, const int count, OpAt op_at, const uint8_
   }
 }
 
-struct PathScratch {
-  uint64_t *colP, *colM;     // LEAF_ENTRIES each
-  int *colS;
-  uint64_t *endP, *endM;     // 2 * blocks each: the left pass, then the right pass
-  int *endS;
-  uint8_t *ops;              // a leaf's operations, last first
-  uint32_t *grow;
-};
-
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
 void k_fs_path(const uint8_t *__restrict__ fwd, const uint8_t *__restrict__ rcs,
                const Ev *__restrict__ evs, const Tp *__restrict__ tps, const uint32_t n_ev,
                const Loc *__restrict__ loc, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
                uint32_t *__restrict__ ntags_out, unsigned long long *__restrict__ cells,
                uint32_t *__restrict__ nleaf_out, uint32_t *__restrict__ nsplit_out,
-               uint64_t *__restrict__ colP_all, uint64_t *__restrict__ colM_all,
-               int *__restrict__ colS_all, uint64_t *__restrict__ endP_all,
-               uint64_t *__restrict__ endM_all, int *__restrict__ endS_all,
-               uint8_t *__restrict__ ops_all, uint32_t *__restrict__ grow_all,
-               const uint32_t max_blocks, const uint64_t ops_bytes, const uint64_t grow_words) {
+               const edw::PathArgs scratch) {
   __shared__ uint32_t s_row[WAVES_PER_BLOCK][LDS_WORDS];
   __shared__ int s_stack[WAVES_PER_BLOCK][STACK_DEPTH][5];
   const int lane = threadIdx.x & 63;
   const int wave = uni((int)(threadIdx.x >> 6));
   const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;
   const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
-  PathScratch W;
-  W.colP = colP_all + gw * LEAF_ENTRIES;
-  W.colM = colM_all + gw * LEAF_ENTRIES;
-  W.colS = colS_all + gw * LEAF_ENTRIES;
-  W.endP = endP_all + gw * 2 * max_blocks;
-  W.endM = endM_all + gw * 2 * max_blocks;
-  W.endS = endS_all + gw * 2 * max_blocks;
-  W.ops = ops_all + gw * ops_bytes;
-  W.grow = grow_words ? grow_all + gw * grow_words : nullptr;
-  int (*stack)[5] = s_stack[wave];
+  const edw::PathScratch W = scratch.wave(gw);
 
   for (uint32_t e = (uint32_t)gw; e < n_ev; e += n_waves) {
     const Loc L = loc[e];
@@ -420,123 +212,16 @@ void k_fs_path(const uint8_t *__restrict__ fwd, const uint8_t *__restrict__ rcs,
     const uint32_t val0 = (uint32_t)(ev.tag_off - tps[ev.tmpl].tag_off);
     const uint32_t cap = ev.tag_cap;
     TagState S{0, 0, 0, -1, 0, CH_NONE, 0};
-    unsigned long long c = 0;
-    uint32_t nleaf = 0, nsplit = 0;
-
-    int sp = 0;
-    if (lane == 0) {
-      stack[0][0] = 0; stack[0][1] = qlen; stack[0][2] = 0; stack[0][3] = tlen;
-      stack[0][4] = uni(L.dist);
-    }
-    sp = 1;
-    __builtin_amdgcn_wave_barrier();
-    while (sp > 0) {
-      sp--;
-      const int q0 = uni(stack[sp][0]), qn = uni(stack[sp][1]), t0 = uni(stack[sp][2]),
-                tn = uni(stack[sp][3]), best = uni(stack[sp][4]);
-      if (qn == 0 || tn == 0) {
-        // an empty side: every remaining base is a DELETE (no query) or an INSERT (no target)
-        const int op = qn == 0 ? OP_DELETE : OP_INSERT;
-        emit_tags(S, qn + tn, [op](int) { return op; }, qp, qlen, tbgn, tlen, ek, evl, val0, cap);
-        continue;
-      }
-      const int nb = (qn + 63) >> 6;
-      const Seq q{qp + q0, qn, 0};
-      if (20ll * nb * tn + 8ll * tn < (long long)FS_LEAF_BYTES) {
-        // a leaf: the whole matrix, then the walk from the corner
-        nleaf++;
-        c += (unsigned long long)qn * tn;
-        const Keep k{W.colP, W.colM, W.colS, nullptr, nullptr, nullptr};
-        (void)dp_pass(q, Seq{tp + t0, tn, 0}, 1, INT_MIN, s_row[wave], W.grow, k);
-        __threadfence();
-        // S(r, c) with the boundary row (c + 1) and column (r + 1)
-        auto score = [&](int r, int cc) -> int {
-          if (r < 0) return cc + 1;
-          if (cc < 0) return r + 1;
-          const size_t at = (size_t)(r >> 6) * (size_t)tn + (size_t)cc;
-          return row_score(W.colP[at], W.colM[at], W.colS[at], r, qn);
-        };
-        int r = qn - 1, cc = tn - 1, nops = 0;
-        int cur = best;
-        while (r >= 0 && cc >= 0) {
-          const int u = score(r - 1, cc), l = score(r, cc - 1), ul = score(r - 1, cc - 1);
-          int op;
-          if (u + 1 == cur) { op = OP_INSERT; r--; cur = u; }
-          else if (l + 1 == cur) { op = OP_DELETE; cc--; cur = l; }
-          else { op = ul == cur ? OP_MATCH : OP_MISMATCH; r--; cc--; cur = ul; }
-          if (lane == 0) W.ops[nops] = (uint8_t)op;
-          nops++;
-        }
-        // at a boundary the rest is flushed: the rows left are INSERTs, the columns DELETEs
-        const int up = r + 1, left = cc + 1;
-        for (int i = lane; i < up + left; i += 64)
-          W.ops[nops + i] = (uint8_t)(up ? OP_INSERT : OP_DELETE);
-        nops += up + left;
-        __threadfence();
-        const uint8_t *ops = W.ops;
-        emit_tags(S, nops, [ops, nops](int i) { return (int)ops[nops - 1 - i]; }, qp, qlen, tbgn,
-                  tlen, ek, evl, val0, cap);
-        __threadfence();                          // the buffer is reused by the next leaf
-        continue;
-      }
-      // a split (obtainAlignmentHirschberg): the last column of the left half and of the
-      // reversed right half, then the first row where the two meet at `best`
-      nsplit++;
-      c += (unsigned long long)qn * tn;
-      const int lw = tn / 2, rw = tn - lw;
-      const Keep kl{nullptr, nullptr, nullptr, W.endP, W.endM, W.endS};
-      const Keep kr{nullptr, nullptr, nullptr, W.endP + max_blocks, W.endM + max_blocks,
-                    W.endS + max_blocks};
-      (void)dp_pass(q, Seq{tp + t0, lw, 0}, 1, INT_MIN, s_row[wave], W.grow, kl);
-      (void)dp_pass(Seq{qp + q0, qn, 1}, Seq{tp + t0 + lw, rw, 1}, 1, INT_MIN, s_row[wave], W.grow, kr);
-      __threadfence();
-      // L[r] = ED(q[0..r], left), R[r] = ED(q[r..], right) = the reversed pass at row qn-1-r
-      auto Lrow = [&](int r) {
-        return row_score(W.endP[r >> 6], W.endM[r >> 6], W.endS[r >> 6], r, qn);
-      };
-      auto Rrow = [&](int r) {
-        const int x = qn - 1 - r;
-        return row_score(W.endP[max_blocks + (x >> 6)], W.endM[max_blocks + (x >> 6)],
-                         W.endS[max_blocks + (x >> 6)], x, qn);
-      };
-      int split = INT_MIN, ls = 0, rs = 0;
-      for (int r0 = 0; r0 <= qn - 2 && split == INT_MIN; r0 += 64) {
-        const int r = r0 + lane;
-        int a = 0, b = 0;
-        bool hit = false;
-        if (r <= qn - 2) { a = Lrow(r); b = Rrow(r + 1); hit = a + b == best; }
-        const uint64_t hm = __ballot(hit);
-        if (hm) {
-          const int first = __ffsll((unsigned long long)hm) - 1;
-          split = r0 + first;
-          ls = __shfl(a, first);
-          rs = __shfl(b, first);
-        }
-      }
-      if (split == INT_MIN) {
-        const int r_top = uni(Rrow(0)), l_bot = uni(Lrow(qn - 1));
-        if (lw + r_top == best) { split = -1; ls = lw; rs = r_top; }
-        else if (l_bot + rw == best) { split = qn - 1; ls = l_bot; rs = rw; }
-        else { split = qn - 1; ls = l_bot; rs = rw; }   // cannot happen: `best` is the distance
-      }
-      split = uni(split); ls = uni(ls); rs = uni(rs);
-      if (sp + 2 <= STACK_DEPTH) {
-        if (lane == 0) {
-          stack[sp][0] = q0 + split + 1; stack[sp][1] = qn - (split + 1);
-          stack[sp][2] = t0 + lw; stack[sp][3] = rw; stack[sp][4] = rs;
-          stack[sp + 1][0] = q0; stack[sp + 1][1] = split + 1;
-          stack[sp + 1][2] = t0; stack[sp + 1][3] = lw; stack[sp + 1][4] = ls;
-        }
-        sp += 2;
-      }
-      __builtin_amdgcn_wave_barrier();
-      __threadfence_block();
-    }
+    const edw::PathStats N = edw::wave_path<5>(
+        Span{qp, qlen}, Span{tp, tlen}, uni(L.dist), W, s_row[wave], s_stack[wave], FS_LEAF_BYTES,
+        [&](int count, auto op_at) {
+          emit_tags(S, count, op_at, qp, qlen, tbgn, tlen, ek, evl, val0, cap);
+        });
     if (lane == 0) {
       ntags_out[e] = S.ntags;
-      cells[e] += c;
-      nleaf_out[e] = nleaf;
-      nsplit_out[e] = nsplit;
+      cells[e] += N.cells;
+      nleaf_out[e] = N.nleaf;
+      nsplit_out[e] = N.nsplit;
     }
   }
 }
@@ -717,10 +402,7 @@ void k_fs_consensus(const Tp *__restrict__ tps, const uint32_t n_tp,
 
 struct fs_ctx : capi::Device {
   fs_params P{};
-  uint32_t first_iid = 0, nreads = 0;
-  std::vector<uint32_t> len;
-  std::vector<uint64_t> off;
-  DevBuf<uint8_t> d_fwd, d_rc;
+  edw::Strands R;
   // the last result
   bool have = false;
   std::vector<uint32_t> tig_ids;
@@ -739,13 +421,6 @@ int check_params(const fs_params *p) {
   return FS_OK;
 }
 
-void free_reads(fs_ctx *c) {
-  c->d_fwd.release(); c->d_rc.release();
-  c->nreads = 0;
-  c->len.clear();
-  c->off.clear();
-}
-
 // One batch of layouts on the device.
 int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &evs,
               const std::vector<uint32_t> &ev_layout, const uint32_t layout0, uint32_t max_q,
@@ -757,19 +432,17 @@ int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &e
   const uint32_t blocks = std::max<uint32_t>(1, std::min<uint32_t>((n_ev + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
                                                                    want_waves / WAVES_PER_BLOCK));
   const uint64_t waves = (uint64_t)blocks * WAVES_PER_BLOCK;
-  const uint32_t max_blocks = (max_q + 63) / 64 + 1;
-  const uint64_t ops_bytes = ((uint64_t)max_q + max_window + 64 + 15) & ~15ull;
-  const uint64_t grow_words = max_window > (uint32_t)LDS_COLUMNS ? ((uint64_t)max_window + 15) / 16 : 0;
+  const edw::PathSize Z = edw::path_size(max_q, max_window, FS_LEAF_BYTES);
 
   DevBuf<Tp> d_tp;
   DevBuf<Ev> d_ev;
   DevBuf<Loc> d_loc;
   DevBuf<unsigned long long> d_cells;
-  DevBuf<uint32_t> d_ntags, d_nleaf, d_nsplit, d_grow, d_vals, d_vals2, d_cov, d_lpos, d_cfl, d_clink,
-      d_outlen;
-  DevBuf<uint64_t> d_keys, d_keys2, d_colP, d_colM, d_endP, d_endM, d_ckey;
-  DevBuf<int> d_colS, d_endS, d_lpidx, d_cscore, d_cback, d_segoff;
-  DevBuf<uint8_t> d_ops, d_out, d_sort;
+  DevBuf<uint32_t> d_ntags, d_nleaf, d_nsplit, d_vals, d_vals2, d_cov, d_lpos, d_cfl, d_clink, d_outlen;
+  DevBuf<uint64_t> d_keys, d_keys2, d_ckey;
+  DevBuf<int> d_lpidx, d_cscore, d_cback, d_segoff;
+  DevBuf<uint8_t> d_out, d_sort;
+  edw::PathBuffers path;
   HIP_TRY(d_tp.alloc(n_tp));
   HIP_TRY(d_ev.alloc(n_ev));
   HIP_TRY(d_loc.alloc(n_ev));
@@ -777,18 +450,11 @@ int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &e
   HIP_TRY(d_ntags.alloc(n_ev));
   HIP_TRY(d_nleaf.alloc(n_ev));
   HIP_TRY(d_nsplit.alloc(n_ev));
-  HIP_TRY(d_grow.alloc(grow_words * waves));
   HIP_TRY(d_keys.alloc(total_tags));
   HIP_TRY(d_keys2.alloc(total_tags));
   HIP_TRY(d_vals.alloc(total_tags));
   HIP_TRY(d_vals2.alloc(total_tags));
-  HIP_TRY(d_colP.alloc((uint64_t)LEAF_ENTRIES * waves));
-  HIP_TRY(d_colM.alloc((uint64_t)LEAF_ENTRIES * waves));
-  HIP_TRY(d_colS.alloc((uint64_t)LEAF_ENTRIES * waves));
-  HIP_TRY(d_endP.alloc(2ull * max_blocks * waves));
-  HIP_TRY(d_endM.alloc(2ull * max_blocks * waves));
-  HIP_TRY(d_endS.alloc(2ull * max_blocks * waves));
-  HIP_TRY(d_ops.alloc(ops_bytes * waves));
+  HIP_TRY(path.alloc(Z, waves));
   HIP_TRY(d_cov.alloc(total_cov));
   HIP_TRY(d_lpos.alloc(total_tags));
   HIP_TRY(d_lpidx.alloc(total_tags));
@@ -800,11 +466,10 @@ int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &e
   HIP_TRY(d_out.alloc(total_out));
   HIP_TRY(d_outlen.alloc(n_tp));
   HIP_TRY(d_segoff.alloc(n_tp + 1));
-  uint64_t scratch = 0;
-  for (size_t b : {d_keys.bytes, d_keys2.bytes, d_vals.bytes, d_vals2.bytes, d_colP.bytes, d_colM.bytes,
-                   d_colS.bytes, d_endP.bytes, d_endM.bytes, d_endS.bytes, d_ops.bytes, d_cov.bytes,
-                   d_lpos.bytes, d_lpidx.bytes, d_ckey.bytes, d_cfl.bytes, d_cscore.bytes,
-                   d_cback.bytes, d_clink.bytes, d_out.bytes, d_grow.bytes})
+  uint64_t scratch = path.bytes();
+  for (size_t b : {d_keys.bytes, d_keys2.bytes, d_vals.bytes, d_vals2.bytes, d_cov.bytes, d_lpos.bytes,
+                   d_lpidx.bytes, d_ckey.bytes, d_cfl.bytes, d_cscore.bytes, d_cback.bytes,
+                   d_clink.bytes, d_out.bytes})
     scratch += b;
   S.scratch_bytes = std::max<uint64_t>(S.scratch_bytes, scratch);
 
@@ -822,16 +487,15 @@ int run_batch(fs_ctx *c, const std::vector<Tp> &tps_in, const std::vector<Ev> &e
   hipEvent_t ev[5];
   for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
   HIP_TRY(hipEventRecord(ev[0], s));
-  hipLaunchKernelGGL(k_fs_locate, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd.p, c->d_rc.p,
-                     d_ev.p, d_tp.p, n_ev, d_loc.p, d_cells.p, grow_words ? d_grow.p : nullptr,
-                     grow_words, 1.0 - c->P.min_identity);
+  hipLaunchKernelGGL(k_fs_locate, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->R.fwd.p, c->R.rc.p,
+                     d_ev.p, d_tp.p, n_ev, d_loc.p, d_cells.p, path.grow_rows(), Z.grow_words,
+                     1.0 - c->P.min_identity);
   hipError_t le = hipGetLastError();
   HIP_TRY(hipEventRecord(ev[1], s));
   if (le == hipSuccess) {
-    hipLaunchKernelGGL(k_fs_path, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->d_fwd.p, c->d_rc.p,
+    hipLaunchKernelGGL(k_fs_path, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->R.fwd.p, c->R.rc.p,
                        d_ev.p, d_tp.p, n_ev, d_loc.p, d_keys.p, d_vals.p, d_ntags.p, d_cells.p,
-                       d_nleaf.p, d_nsplit.p, d_colP.p, d_colM.p, d_colS.p, d_endP.p, d_endM.p,
-                       d_endS.p, d_ops.p, d_grow.p, max_blocks, ops_bytes, grow_words);
+                       d_nleaf.p, d_nsplit.p, path.args());
     le = hipGetLastError();
   }
   HIP_TRY(hipEventRecord(ev[2], s));
@@ -935,45 +599,8 @@ int fs_load_reads_device(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const u
   if (!c) return fail(FS_ERR_BAD_PARAM, "null context");
   if (int rc = capi::check_device_reads(first_iid, nreads, d_bases, d_offsets, h_lengths)) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  free_reads(c);
   c->have = false;
-  std::vector<uint64_t> off(nreads);
-  uint64_t total = 0;
-  for (uint32_t i = 0; i < nreads; i++) {
-    if (h_lengths[i] > MAX_READLEN)
-      return fail(FS_ERR_BAD_INPUT, "read %u is %u bases, beyond AS_MAX_READLEN", first_iid + i,
-                  h_lengths[i]);
-    off[i] = total;
-    total += h_lengths[i];
-  }
-  DevBuf<uint32_t> bad, d_len;
-  DevBuf<uint64_t> d_off;
-  HIP_TRY(bad.alloc(1));
-  HIP_TRY(d_len.alloc(nreads));
-  HIP_TRY(d_off.alloc(nreads));
-  HIP_TRY(c->d_fwd.alloc(total));
-  HIP_TRY(c->d_rc.alloc(total));
-  HIP_TRY(hipMemsetAsync(bad.p, 0, 4, c->stream));
-  uint32_t h_bad = 0;
-  if (nreads) {
-    HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
-    const uint32_t grid = std::min<uint32_t>(nreads, 4096);
-    hipLaunchKernelGGL(k_fs_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, d_off.p,
-                       d_len.p, nreads, c->d_fwd.p, c->d_rc.p, bad.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (h_bad) {
-    free_reads(c);
-    return fail(FS_ERR_BAD_INPUT, "a read holds a byte outside ACGTN");
-  }
-  c->first_iid = first_iid;
-  c->nreads = nreads;
-  c->len.assign(h_lengths, h_lengths + nreads);
-  c->off = off;
-  return FS_OK;
+  return edw::load_strands(c->R, c->stream, false, first_iid, nreads, d_bases, d_offsets, h_lengths);
 }
 
 int fs_load_reads(fs_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
@@ -994,7 +621,7 @@ int fs_consensus(fs_ctx *c, const fs_layout *layouts, uint64_t n_layouts, const 
   HIP_TRY(hipSetDevice(c->device));
   c->have = false;
   c->S = fs_stats{};
-  auto loaded = [&](uint32_t id) { return id >= c->first_iid && id - c->first_iid < c->nreads; };
+  auto loaded = [&](uint32_t id) { return id >= c->R.first_iid && id - c->R.first_iid < c->R.nreads; };
   // the checks the reference leaves to its assertions
   for (uint64_t i = 0; i < n_layouts; i++) {
     const fs_layout &l = layouts[i];
@@ -1013,7 +640,7 @@ int fs_consensus(fs_ctx *c, const fs_layout *layouts, uint64_t n_layouts, const 
       if (!loaded(ch.ident))
         return fail(FS_ERR_BAD_INPUT, "layout %llu: child read %u is not loaded",
                     (unsigned long long)i, ch.ident);
-      const uint32_t len = c->len[ch.ident - c->first_iid];
+      const uint32_t len = c->R.len[ch.ident - c->R.first_iid];
       if (ch.askip < 0 || ch.bskip < 0 || (uint64_t)ch.askip + (uint64_t)ch.bskip > len)
         return fail(FS_ERR_BAD_INPUT, "layout %llu: child %u skips %d + %d of %u bases",
                     (unsigned long long)i, ch.ident, ch.askip, ch.bskip, len);
@@ -1042,8 +669,8 @@ int fs_consensus(fs_ctx *c, const fs_layout *layouts, uint64_t n_layouts, const 
     const uint64_t first = i;
     for (; i < n_layouts; i++) {
       const fs_layout &l = layouts[i];
-      const uint32_t tr = l.tig_id - c->first_iid;
-      const int32_t tlen = (int32_t)c->len[tr];
+      const uint32_t tr = l.tig_id - c->R.first_iid;
+      const int32_t tlen = (int32_t)c->R.len[tr];
       std::vector<Ev> mine;
       uint64_t my_tags = 0;
       uint32_t skipped = 0;
@@ -1051,14 +678,14 @@ int fs_consensus(fs_ctx *c, const fs_layout *layouts, uint64_t n_layouts, const 
         Ev e{};
         int32_t len, bgn, end;
         if (k == 0) {                               // the template, placed on itself
-          e.seq = c->off[tr];
+          e.seq = c->R.off[tr];
           len = tlen; bgn = 0; end = tlen;
         } else {
           const fs_child &ch = children[l.first_child + k - 1];
-          const uint32_t r = ch.ident - c->first_iid;
+          const uint32_t r = ch.ident - c->R.first_iid;
           e.rc = ch.reverse ? 1 : 0;
-          e.seq = c->off[r] + (uint32_t)ch.askip;
-          len = (int32_t)c->len[r] - ch.askip - ch.bskip;
+          e.seq = c->R.off[r] + (uint32_t)ch.askip;
+          len = (int32_t)c->R.len[r] - ch.askip - ch.bskip;
           bgn = ch.min; end = ch.max;
         }
         if (len > tlen) len = tlen;                 // falconConsensus-alignTag.C:130-134
@@ -1084,7 +711,7 @@ int fs_consensus(fs_ctx *c, const fs_layout *layouts, uint64_t n_layouts, const 
         return fail(FS_ERR_UNSUPPORTED, "layout %llu needs %llu tag slots, more than 2^31",
                     (unsigned long long)i, (unsigned long long)my_tags);
       Tp t{};
-      t.seq = c->off[tr];
+      t.seq = c->R.off[tr];
       t.tag_off = tags;
       t.cov_off = cov;
       t.out_off = out;

@@ -1,29 +1,21 @@
 // gfa.hip -- libcanu_gfa.so: canu's alignGFA (src/gfa/alignGFA.C) on gfx950.  include/canu_gfa.h
 // says what is reproduced; this is how.
 //
-//   k_gfa_hw     one wave per alignment: edlib's EDLIB_MODE_HW / EDLIB_TASK_LOC result in closed
-//                form.  An infix pass gives the distance and the first best end column; where
-//                the caller needs it, a prefix pass of the reversed query over the reversed
-//                target up to that column gives the longest start.  It serves checkLink's two
-//                extension steps (one launch each, all links together) and every round of
-//                checkRecord_align's loop (one launch per round over the calls still open).
+//   k_gfa_hw     one wave per alignment: edlib's EDLIB_MODE_HW / EDLIB_TASK_LOC result
+//                (edlib_wave.h's wave_locate), with the start only where the caller needs it.
+//                It serves checkLink's two extension steps (one launch each, all links
+//                together) and every round of checkRecord_align's loop (one launch per round
+//                over the calls still open).
 //   k_gfa_path   one wave per link: the global distance, then -- within 2 * maxEdit --
-//                obtainAlignment's recursion with an explicit stack in LDS, as fs.hip's k_fs_path
-//                runs it: a split keeps Pv / Mv and the end score of every 64-row block of the
-//                two last columns and takes the first row where they meet at the distance; a
-//                leaf keeps every column and walks up / left / diagonal from the corner.  The
-//                operations of a leaf (one byte each, backwards) become CIGAR runs 64 at a time
-//                with ballots; a run that crosses a chunk or a leaf is carried in the wave's
-//                state.  Per-base operations never leave the device.
+//                obtainAlignment's recursion (edlib_wave.h's wave_path, leaves under
+//                GFA_LEAF_BYTES).  Its operations become CIGAR runs 64 at a time with ballots;
+//                a run that crosses a chunk or a leaf is carried in the wave's state.  Per-base
+//                operations never leave the device.
 //
 // An oriented tig is never copied: a span of a reversed tig is read backwards through the
 // complement, with N as a sixth symbol (the NUL of reverseComplementCopy) that equals only
 // itself.  The host's part of a link or record is the reference's double arithmetic
 // (gfa_host.h) between the launches.
-//
-// The aligner core (dp_pass) is that of pair.hip and fs.hip: Myers' bit-vector recurrence, lane b
-// holding rows 64b..64b+63, columns as a skewed wavefront, 4096-row stripes, the stripe boundary
-// row in LDS up to 16384 columns and in a global row beyond.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,22 +28,22 @@
 
 #include "../../include/canu_gfa.h"
 #include "capi_common.h"
+#include "edlib_launch.h"
 #include "gfa_host.h"
 
 namespace {
 
 using capi::fail;
+using edw::CODE_NUL;
+using edw::LDS_WORDS;
+using edw::OP_DELETE;
+using edw::OP_INSERT;
+using edw::OP_MATCH;
+using edw::STACK_DEPTH;
+using edw::uni;
+using edw::WAVES_PER_BLOCK;
 
 CAPI_SAME_CODES(GFA);
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr int STRIPE_ROWS = 4096;                     // 64 lanes x 64 rows
-constexpr int LDS_COLUMNS = 16384;                    // stripe-boundary row kept in LDS
-constexpr int LDS_WORDS = LDS_COLUMNS / 16;           // 2 bits per column
-constexpr int LEAF_ENTRIES = GFA_LEAF_BYTES / 20 + 1; // block columns of a leaf
-constexpr int STACK_DEPTH = 40;                       // the target halves at every level
-
-enum : int { OP_MATCH = 0, OP_INSERT = 1, OP_DELETE = 2, OP_MISMATCH = 3 };   // EDLIB_EDOP_*
-enum : int { CODE_N = 4, CODE_NUL = 5, CODE_PAD = 7 };
 
 struct Span {                // a stretch of a tig, in the tig's own coordinates
   uint64_t off;              // its first byte in the set's array
@@ -84,31 +76,7 @@ struct NwOut {
   unsigned long long cells;
 };
 
-// ------------------------------------------------------------------ tig encoding
-
-__global__ void k_gfa_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
-                             const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ len,
-                             uint32_t ntigs, uint8_t *__restrict__ codes, uint32_t *__restrict__ bad) {
-  for (uint32_t r = blockIdx.x; r < ntigs; r += gridDim.x) {
-    const uint8_t *s = bases + src_off[r];
-    const uint64_t d = dst_off[r];
-    const uint32_t L = len[r];
-    for (uint32_t i = threadIdx.x; i < L; i += blockDim.x) {
-      const uint8_t ch = s[i];
-      uint8_t c = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : CODE_N;
-      if (c == CODE_N && ch != 'N') atomicOr(bad, 1u);
-      codes[d + i] = c;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ the aligner
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ int dpp_from_lower(int v, int lane0) {   // lane l <- v[l-1]
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xf, 0xf, false);
-}
+// ------------------------------------------------------------------ the spans
 
 struct Seq {                 // a span as the aligner reads it
   const uint8_t *p;
@@ -136,142 +104,7 @@ __device__ __forceinline__ Ori ori_of(const Span s, const uint8_t *tigT, const u
   return Ori{((s.flags & 2u) ? tigC : tigT) + s.off, s.n, (int)(s.flags & 1u)};
 }
 
-struct PassOut {
-  int best, bestcol;         // minimum of the bottom row, the first column attaining it
-  int lastcol;               // last column whose bottom-row score == want (-1: none)
-  int fin;                   // bottom-row score at the last column
-};
-
-// What a pass leaves behind besides its bottom row.  Block g is rows 64g..64g+63.
-struct Keep {
-  uint64_t *colP, *colM;     // leaf: Pv / Mv of block g after column j at [g * n + j]
-  int *colS;                 //       and the score of the block's last row there
-  uint64_t *endP, *endM;     // split: Pv / Mv of block g after the last column at [g]
-  int *endS;                 //        and the score of the block's last row there
-};
-
-// Bottom row of the edit-distance matrix of q (rows) against t (columns); top_hin 0 lets an
-// alignment start at any column (infix), 1 charges every skipped target base (prefix, global).
-// Needs q.n >= 1, t.n >= 1.  Every lane of the wave is in, with the same arguments.
-__device__ PassOut dp_pass(const Seq q, const Seq t, const int top_hin, const int want,
-                           uint32_t *lrow, uint32_t *grow, const Keep keep) {
-  const int lane = threadIdx.x & 63;
-  const int m = q.n, n = t.n;
-  const int nstripes = (m + STRIPE_ROWS - 1) / STRIPE_ROWS;
-  const bool use_g = n > LDS_COLUMNS;
-  int best = INT_MAX, bestcol = -1, lastcol = -1, sc = m;
-  int lb = 0;
-  for (int st = 0; st < nstripes; st++) {
-    const int r0 = st * STRIPE_ROWS;
-    const int rows = min(STRIPE_ROWS, m - r0);
-    const int nb = (rows + 63) >> 6;
-    const bool last = st == nstripes - 1;
-    lb = nb - 1;
-    uint64_t pe0 = 0, pe1 = 0, pe2 = 0, pe3 = 0, pe4 = 0, pe5 = 0;
-    for (int c = 0; c < nb; c++) {
-      const int i = r0 + c * 64 + lane;
-      const int code = i < m ? q.at(i) : CODE_PAD;
-      const uint64_t b0 = __ballot(code == 0), b1 = __ballot(code == 1),
-                     b2 = __ballot(code == 2), b3 = __ballot(code == 3),
-                     b4 = __ballot(code == CODE_N), b5 = __ballot(code == CODE_NUL);
-      if (lane == c) { pe0 = b0; pe1 = b1; pe2 = b2; pe3 = b3; pe4 = b4; pe5 = b5; }
-    }
-    uint64_t Pv = ~0ull, Mv = 0;
-    const bool trk = last && lane == lb;
-    // the last row of this lane's block, whose score the lane follows along the columns (the
-    // boundary column holds row + 1)
-    const int lrow_abs = min(r0 + 64 * (lane + 1), m) - 1;
-    const int rr = lane < nb ? (lrow_abs & 63) : 63;
-    sc = lrow_abs + 1;
-    const size_t gblk = (size_t)(st * 64 + lane);
-    int x = 1;                                  // (hout + 1) | base << 2, handed to lane + 1
-    uint32_t cur = lane < n ? (uint32_t)t.at(lane) : (uint32_t)CODE_PAD;
-    uint32_t nxt = 64 + lane < n ? (uint32_t)t.at(64 + lane) : (uint32_t)CODE_PAD;
-    uint32_t hw = 0, acc = 0;
-    const int nsteps = n + nb - 1;
-    for (int s = 0; s < nsteps; s++) {
-      if ((s & 63) == 0 && s > 0) {
-        cur = nxt;
-        const int c = s + 64 + lane;
-        nxt = c < n ? (uint32_t)t.at(c) : (uint32_t)CODE_PAD;
-      }
-      const int base0 = __builtin_amdgcn_readlane((int)cur, s & 63);
-      int hin0 = top_hin;
-      if (st > 0) {
-        if ((s & 15) == 0 && s < n) hw = use_g ? grow[s >> 4] : lrow[s >> 4];
-        hin0 = (int)((hw >> (2 * (s & 15))) & 3u) - 1;
-      }
-      const int xin = dpp_from_lower(x, (hin0 + 1) | (base0 << 2));
-      const int j = s - lane;
-      const bool act = lane < nb && j >= 0 && j < n;
-      int d = 0;
-      if (act) {
-        const int hin = (xin & 3) - 1;
-        const int b = xin >> 2;
-        const uint64_t s0 = 0 - (uint64_t)(b & 1), s1 = 0 - (uint64_t)((b >> 1) & 1),
-                       s2 = 0 - (uint64_t)(b >> 2);
-        const uint64_t e01 = (pe0 & ~s0) | (pe1 & s0), e23 = (pe2 & ~s0) | (pe3 & s0);
-        const uint64_t e45 = (pe4 & ~s0) | (pe5 & s0);
-        const uint64_t e03 = (e01 & ~s1) | (e23 & s1);
-        uint64_t Eq = (e03 & ~s2) | (e45 & s2);
-        const uint64_t neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
-        const uint64_t Xv = Eq | Mv;
-        Eq |= neg;
-        const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-        uint64_t Ph = Mv | ~(Xh | Pv);
-        uint64_t Mh = Pv & Xh;
-        d = (int)((Ph >> 63) & 1) - (int)((Mh >> 63) & 1);
-        sc += (int)((Ph >> rr) & 1) - (int)((Mh >> rr) & 1);
-        Ph = (Ph << 1) | pos;
-        Mh = (Mh << 1) | neg;
-        Pv = Mh | ~(Xv | Ph);
-        Mv = Ph & Xv;
-        if (trk) {
-          if (sc < best) { best = sc; bestcol = j; }
-          if (sc == want) lastcol = j;
-        }
-        if (keep.colP) {
-          const size_t at = gblk * (size_t)n + (size_t)j;
-          keep.colP[at] = Pv;
-          keep.colM[at] = Mv;
-          keep.colS[at] = sc;
-        }
-        if (!last && lane == lb) {              // lane 63: the next stripe's top boundary
-          acc |= (uint32_t)(d + 1) << (2 * (j & 15));
-          if ((j & 15) == 15 || j == n - 1) {
-            if (use_g) grow[j >> 4] = acc; else lrow[j >> 4] = acc;
-            acc = 0;
-          }
-        }
-      }
-      x = (d + 1) | (xin & ~3);
-    }
-    if (keep.endP && lane < nb) {
-      keep.endP[gblk] = Pv;
-      keep.endM[gblk] = Mv;
-      keep.endS[gblk] = sc;
-    }
-    if (!last) __threadfence();                 // lane 63's row is read by every lane next
-  }
-  PassOut o;
-  o.best = __shfl(best, lb);
-  o.bestcol = __shfl(bestcol, lb);
-  o.lastcol = __shfl(lastcol, lb);
-  o.fin = __shfl(sc, lb);
-  return o;
-}
-
-// Score of row r (0 <= r < m) from the block's end score and its Pv / Mv: the rows above the
-// block's last row down to r + 1 are taken back.
-__device__ __forceinline__ int row_score(const uint64_t P, const uint64_t M, const int end_score,
-                                         const int r, const int m) {
-  const int b = r >> 6;
-  const int lastbit = (min(64 * (b + 1), m) - 1) & 63;
-  const uint64_t upto = lastbit == 63 ? ~0ull : ((1ull << (lastbit + 1)) - 1);
-  const uint64_t above = (r & 63) == 63 ? 0ull : (~0ull << ((r & 63) + 1));
-  const uint64_t hi = above & upto;
-  return end_score - __popcll(P & hi) + __popcll(M & hi);
-}
+// ------------------------------------------------------------------ the location
 
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
 void k_gfa_hw(const uint8_t *__restrict__ tigT, const uint8_t *__restrict__ tigC,
@@ -283,26 +116,16 @@ void k_gfa_hw(const uint8_t *__restrict__ tigT, const uint8_t *__restrict__ tigC
   const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;
   const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
   uint32_t *grow = scratch ? scratch + gw * scratch_words : nullptr;
-  const Keep none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   for (uint32_t e = (uint32_t)gw; e < n_jobs; e += n_waves) {
     const HwJob jb = jobs[e];
-    const Ori q = ori_of(jb.q, tigT, tigC), t = ori_of(jb.t, tigT, tigC);
-    const int m = uni(q.n), n = uni(t.n);
-    const PassOut f = dp_pass(q.fwd(), t.fwd(), 0, INT_MIN, s_row[wave], grow, none);
-    unsigned long long c = (unsigned long long)m * n;
-    const int best = uni(f.best), end = uni(f.bestcol);
-    HwOut o{-1, 0, 0, 0, 0};
-    if (best <= uni(jb.k)) {
-      o.dist = best;
-      o.end = end;
-      if (uni(jb.need_start)) {
-        // the last column of the reversed prefix pass still at `best` is the longest alignment
-        const PassOut r = dp_pass(q.bwd(), t.sub(0, end + 1).bwd(), 1, best, s_row[wave], grow, none);
-        c += (unsigned long long)m * (end + 1);
-        o.start = end - uni(r.lastcol);
-      }
+    const edw::Located L = edw::wave_locate<6>(ori_of(jb.q, tigT, tigC), ori_of(jb.t, tigT, tigC),
+                                               uni(jb.k), uni(jb.need_start) != 0, s_row[wave], grow);
+    HwOut o{-1, 0, 0, 0, L.cells};
+    if (L.ok) {
+      o.dist = L.dist;
+      o.start = L.start;
+      o.end = L.end;
     }
-    o.cells = c;
     if (lane == 0) out[e] = o;
   }
 }
@@ -359,171 +182,42 @@ __device__ void emit_runs(RunState &S, const int count, OpAt op_at, gfa_run *__r
   S.total += (uint32_t)count;
 }
 
-struct PathScratch {
-  uint64_t *colP, *colM;     // LEAF_ENTRIES each
-  int *colS;
-  uint64_t *endP, *endM;     // 2 * blocks each: the left pass, then the right pass
-  int *endS;
-  uint8_t *ops;              // a leaf's operations, last first
-  uint32_t *grow;
-};
-
 __global__ __launch_bounds__(64 * WAVES_PER_BLOCK)
 void k_gfa_path(const uint8_t *__restrict__ tigT, const uint8_t *__restrict__ tigC,
                 const NwJob *__restrict__ jobs, const uint32_t n_jobs, NwOut *__restrict__ out,
-                gfa_run *__restrict__ runs_all,
-                uint64_t *__restrict__ colP_all, uint64_t *__restrict__ colM_all,
-                int *__restrict__ colS_all, uint64_t *__restrict__ endP_all,
-                uint64_t *__restrict__ endM_all, int *__restrict__ endS_all,
-                uint8_t *__restrict__ ops_all, uint32_t *__restrict__ grow_all,
-                const uint32_t max_blocks, const uint64_t ops_bytes, const uint64_t grow_words) {
+                gfa_run *__restrict__ runs_all, const edw::PathArgs scratch) {
   __shared__ uint32_t s_row[WAVES_PER_BLOCK][LDS_WORDS];
   __shared__ int s_stack[WAVES_PER_BLOCK][STACK_DEPTH][5];
   const int lane = threadIdx.x & 63;
   const int wave = uni((int)(threadIdx.x >> 6));
   const uint64_t gw = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wave;
   const uint32_t n_waves = gridDim.x * WAVES_PER_BLOCK;
-  PathScratch W;
-  W.colP = colP_all + gw * LEAF_ENTRIES;
-  W.colM = colM_all + gw * LEAF_ENTRIES;
-  W.colS = colS_all + gw * LEAF_ENTRIES;
-  W.endP = endP_all + gw * 2 * max_blocks;
-  W.endM = endM_all + gw * 2 * max_blocks;
-  W.endS = endS_all + gw * 2 * max_blocks;
-  W.ops = ops_all + gw * ops_bytes;
-  W.grow = grow_words ? grow_all + gw * grow_words : nullptr;
-  int (*stack)[5] = s_stack[wave];
-  const Keep none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const edw::PathScratch W = scratch.wave(gw);
 
   for (uint32_t e = (uint32_t)gw; e < n_jobs; e += n_waves) {
     const NwJob jb = jobs[e];
-    const Ori Q = ori_of(jb.q, tigT, tigC), T = ori_of(jb.t, tigT, tigC);
-    const int qlen = uni(Q.n), tlen = uni(T.n);
+    Ori Q = ori_of(jb.q, tigT, tigC), T = ori_of(jb.t, tigT, tigC);
+    Q.n = uni(Q.n);
+    T.n = uni(T.n);
     gfa_run *runs = runs_all + jb.run_off;
     const uint32_t cap = jb.run_cap;
-    unsigned long long c = (unsigned long long)qlen * tlen;
-    const PassOut g = dp_pass(Q.fwd(), T.fwd(), 1, INT_MIN, s_row[wave], W.grow, none);
+    const unsigned long long c = (unsigned long long)Q.n * T.n;
+    const edw::PassOut g = edw::dp_pass<6>(Q.fwd(), T.fwd(), 1, INT_MIN, s_row[wave], W.grow,
+                                           edw::NoKeep{});
     const int dist = uni(g.fin);
     if (dist > uni(jb.k)) {
       if (lane == 0) out[e] = NwOut{-1, 0, 0, 0, 0, 0, c};
       continue;
     }
     RunState S{-1, 0, 0, 0};
-    uint32_t nleaf = 0, nsplit = 0;
-
-    int sp = 0;
-    if (lane == 0) {
-      stack[0][0] = 0; stack[0][1] = qlen; stack[0][2] = 0; stack[0][3] = tlen;
-      stack[0][4] = dist;
-    }
-    sp = 1;
-    __builtin_amdgcn_wave_barrier();
-    while (sp > 0) {
-      sp--;
-      const int q0 = uni(stack[sp][0]), qn = uni(stack[sp][1]), t0 = uni(stack[sp][2]),
-                tn = uni(stack[sp][3]), best = uni(stack[sp][4]);
-      if (qn == 0 || tn == 0) {
-        // an empty side: every remaining base is a DELETE (no query) or an INSERT (no target)
-        const int op = qn == 0 ? OP_DELETE : OP_INSERT;
-        emit_runs(S, qn + tn, [op](int) { return op; }, runs, cap);
-        continue;
-      }
-      const int nb = (qn + 63) >> 6;
-      const Ori q = Q.sub(q0, qn);
-      if (20ll * nb * tn + 8ll * tn < (long long)GFA_LEAF_BYTES) {
-        // a leaf: the whole matrix, then the walk from the corner
-        nleaf++;
-        c += (unsigned long long)qn * tn;
-        const Keep k{W.colP, W.colM, W.colS, nullptr, nullptr, nullptr};
-        (void)dp_pass(q.fwd(), T.sub(t0, tn).fwd(), 1, INT_MIN, s_row[wave], W.grow, k);
-        __threadfence();
-        // S(r, c) with the boundary row (c + 1) and column (r + 1)
-        auto score = [&](int r, int cc) -> int {
-          if (r < 0) return cc + 1;
-          if (cc < 0) return r + 1;
-          const size_t at = (size_t)(r >> 6) * (size_t)tn + (size_t)cc;
-          return row_score(W.colP[at], W.colM[at], W.colS[at], r, qn);
-        };
-        int r = qn - 1, cc = tn - 1, nops = 0;
-        int cur = best;
-        while (r >= 0 && cc >= 0) {
-          const int u = score(r - 1, cc), l = score(r, cc - 1), ul = score(r - 1, cc - 1);
-          int op;
-          if (u + 1 == cur) { op = OP_INSERT; r--; cur = u; }
-          else if (l + 1 == cur) { op = OP_DELETE; cc--; cur = l; }
-          else { op = ul == cur ? OP_MATCH : OP_MISMATCH; r--; cc--; cur = ul; }
-          if (lane == 0) W.ops[nops] = (uint8_t)op;
-          nops++;
-        }
-        // at a boundary the rest is flushed: the rows left are INSERTs, the columns DELETEs
-        const int up = r + 1, left = cc + 1;
-        for (int i = lane; i < up + left; i += 64)
-          W.ops[nops + i] = (uint8_t)(up ? OP_INSERT : OP_DELETE);
-        nops += up + left;
-        __threadfence();
-        const uint8_t *ops = W.ops;
-        emit_runs(S, nops, [ops, nops](int i) { return (int)ops[nops - 1 - i]; }, runs, cap);
-        __threadfence();                          // the buffer is reused by the next leaf
-        continue;
-      }
-      // a split (obtainAlignmentHirschberg): the last column of the left half and of the
-      // reversed right half, then the first row where the two meet at `best`
-      nsplit++;
-      c += (unsigned long long)qn * tn;
-      const int lw = tn / 2, rw = tn - lw;
-      const Keep kl{nullptr, nullptr, nullptr, W.endP, W.endM, W.endS};
-      const Keep kr{nullptr, nullptr, nullptr, W.endP + max_blocks, W.endM + max_blocks,
-                    W.endS + max_blocks};
-      (void)dp_pass(q.fwd(), T.sub(t0, lw).fwd(), 1, INT_MIN, s_row[wave], W.grow, kl);
-      (void)dp_pass(q.bwd(), T.sub(t0 + lw, rw).bwd(), 1, INT_MIN, s_row[wave], W.grow, kr);
-      __threadfence();
-      // L[r] = ED(q[0..r], left), R[r] = ED(q[r..], right) = the reversed pass at row qn-1-r
-      auto Lrow = [&](int r) {
-        return row_score(W.endP[r >> 6], W.endM[r >> 6], W.endS[r >> 6], r, qn);
-      };
-      auto Rrow = [&](int r) {
-        const int x = qn - 1 - r;
-        return row_score(W.endP[max_blocks + (x >> 6)], W.endM[max_blocks + (x >> 6)],
-                         W.endS[max_blocks + (x >> 6)], x, qn);
-      };
-      int split = INT_MIN, ls = 0, rs = 0;
-      for (int r0 = 0; r0 <= qn - 2 && split == INT_MIN; r0 += 64) {
-        const int r = r0 + lane;
-        int a = 0, b = 0;
-        bool hit = false;
-        if (r <= qn - 2) { a = Lrow(r); b = Rrow(r + 1); hit = a + b == best; }
-        const uint64_t hm = __ballot(hit);
-        if (hm) {
-          const int first = __ffsll((unsigned long long)hm) - 1;
-          split = r0 + first;
-          ls = __shfl(a, first);
-          rs = __shfl(b, first);
-        }
-      }
-      if (split == INT_MIN) {
-        const int r_top = uni(Rrow(0)), l_bot = uni(Lrow(qn - 1));
-        if (lw + r_top == best) { split = -1; ls = lw; rs = r_top; }
-        else if (l_bot + rw == best) { split = qn - 1; ls = l_bot; rs = rw; }
-        else { split = qn - 1; ls = l_bot; rs = rw; }   // cannot happen: `best` is the distance
-      }
-      split = uni(split); ls = uni(ls); rs = uni(rs);
-      if (sp + 2 <= STACK_DEPTH) {
-        if (lane == 0) {
-          stack[sp][0] = q0 + split + 1; stack[sp][1] = qn - (split + 1);
-          stack[sp][2] = t0 + lw; stack[sp][3] = rw; stack[sp][4] = rs;
-          stack[sp + 1][0] = q0; stack[sp + 1][1] = split + 1;
-          stack[sp + 1][2] = t0; stack[sp + 1][3] = lw; stack[sp + 1][4] = ls;
-        }
-        sp += 2;
-      }
-      __builtin_amdgcn_wave_barrier();
-      __threadfence_block();
-    }
+    const edw::PathStats N = edw::wave_path<6>(
+        Q, T, dist, W, s_row[wave], s_stack[wave], GFA_LEAF_BYTES,
+        [&](int count, auto op_at) { emit_runs(S, count, op_at, runs, cap); });
     if (S.cnt > 0) {
       if (lane == 0 && S.nruns < cap) runs[S.nruns] = gfa_run{S.cnt, run_op(S.cls)};
       S.nruns++;
     }
-    if (lane == 0) out[e] = NwOut{dist, (int32_t)S.total, S.nruns, nleaf, nsplit, 0, c};
+    if (lane == 0) out[e] = NwOut{dist, (int32_t)S.total, S.nruns, N.nleaf, N.nsplit, 0, c + N.cells};
   }
 }
 
@@ -579,7 +273,7 @@ int run_hw(gfa_ctx *c, const std::vector<HwJob> &jobs, std::vector<HwOut> &out, 
   for (const HwJob &j : jobs) max_t = std::max<uint32_t>(max_t, (uint32_t)j.t.n);
   const uint32_t blocks = blocks_for(c, n);
   const uint64_t waves = (uint64_t)blocks * WAVES_PER_BLOCK;
-  const uint64_t grow_words = max_t > (uint32_t)LDS_COLUMNS ? ((uint64_t)max_t + 15) / 16 : 0;
+  const uint64_t grow_words = edw::grow_words(max_t);
   DevBuf<HwJob> d_jobs;
   DevBuf<HwOut> d_out;
   DevBuf<uint32_t> d_grow;
@@ -626,32 +320,16 @@ int run_path(gfa_ctx *c, const std::vector<NwJob> &jobs, uint64_t total_runs, st
   }
   const uint32_t blocks = blocks_for(c, n);
   const uint64_t waves = (uint64_t)blocks * WAVES_PER_BLOCK;
-  const uint32_t max_blocks = (max_q + 63) / 64 + 1;
-  const uint64_t ops_bytes = ((uint64_t)max_q + max_t + 64 + 15) & ~15ull;
-  const uint64_t grow_words = max_t > (uint32_t)LDS_COLUMNS ? ((uint64_t)max_t + 15) / 16 : 0;
   DevBuf<NwJob> d_jobs;
   DevBuf<NwOut> d_out;
   DevBuf<gfa_run> d_runs;
-  DevBuf<uint64_t> d_colP, d_colM, d_endP, d_endM;
-  DevBuf<int> d_colS, d_endS;
-  DevBuf<uint8_t> d_ops;
-  DevBuf<uint32_t> d_grow;
+  edw::PathBuffers path;
   HIP_TRY(d_jobs.alloc(n));
   HIP_TRY(d_out.alloc(n));
   HIP_TRY(d_runs.alloc(total_runs));
-  HIP_TRY(d_colP.alloc((uint64_t)LEAF_ENTRIES * waves));
-  HIP_TRY(d_colM.alloc((uint64_t)LEAF_ENTRIES * waves));
-  HIP_TRY(d_colS.alloc((uint64_t)LEAF_ENTRIES * waves));
-  HIP_TRY(d_endP.alloc(2ull * max_blocks * waves));
-  HIP_TRY(d_endM.alloc(2ull * max_blocks * waves));
-  HIP_TRY(d_endS.alloc(2ull * max_blocks * waves));
-  HIP_TRY(d_ops.alloc(ops_bytes * waves));
-  HIP_TRY(d_grow.alloc(grow_words * waves));
-  uint64_t scratch = 0;
-  for (size_t b : {d_jobs.bytes, d_out.bytes, d_runs.bytes, d_colP.bytes, d_colM.bytes, d_colS.bytes,
-                   d_endP.bytes, d_endM.bytes, d_endS.bytes, d_ops.bytes, d_grow.bytes})
-    scratch += b;
-  c->S.scratch_bytes = std::max<uint64_t>(c->S.scratch_bytes, scratch);
+  HIP_TRY(path.alloc(edw::path_size(max_q, max_t, GFA_LEAF_BYTES), waves));
+  c->S.scratch_bytes = std::max<uint64_t>(c->S.scratch_bytes,
+                                          d_jobs.bytes + d_out.bytes + d_runs.bytes + path.bytes());
   hipStream_t s = c->stream;
   Event e0, e1;
   HIP_TRY(e0.create());
@@ -659,9 +337,7 @@ int run_path(gfa_ctx *c, const std::vector<NwJob> &jobs, uint64_t total_runs, st
   HIP_TRY(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(NwJob), hipMemcpyHostToDevice, s));
   HIP_TRY(hipEventRecord(e0, s));
   hipLaunchKernelGGL(k_gfa_path, dim3(blocks), dim3(64 * WAVES_PER_BLOCK), 0, s, c->sets[0].d_codes.p,
-                     c->sets[1].d_codes.p, d_jobs.p, n, d_out.p, d_runs.p, d_colP.p, d_colM.p,
-                     d_colS.p, d_endP.p, d_endM.p, d_endS.p, d_ops.p, d_grow.p, max_blocks, ops_bytes,
-                     grow_words);
+                     c->sets[1].d_codes.p, d_jobs.p, n, d_out.p, d_runs.p, path.args());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipMemcpyAsync(out.data(), d_out.p, n * sizeof(NwOut), hipMemcpyDeviceToHost, s));
@@ -950,8 +626,8 @@ int gfa_load_tigs(gfa_ctx *c, int which, uint32_t n, const uint8_t *bases, const
   if (n) {
     HIP_TRY(hipMemcpyAsync(d_off.p, off.data(), n * 8ull, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_len.p, lengths, n * 4ull, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_gfa_encode, dim3(std::min<uint32_t>(n, 4096)), dim3(256), 0, c->stream, d_b.p,
-                       d_o.p, d_off.p, d_len.p, n, ts.d_codes.p, bad.p);
+    hipLaunchKernelGGL(edw::k_encode, dim3(std::min<uint32_t>(n, 4096)), dim3(256), 0, c->stream, d_b.p,
+                       d_o.p, d_off.p, d_len.p, n, ts.d_codes.p, (uint8_t *)nullptr, bad.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
   }

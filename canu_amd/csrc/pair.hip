@@ -4,15 +4,8 @@
 // dependent edit-distance passes (edlibAlign, restated in include/canu_pair.h) with the hang
 // arithmetic between them, so nothing goes back to the host between passes.
 //
-// The DP is Myers' bit-vector recurrence (Myers 1999; the block step of edlib.C:276-330).
-// Lane b holds Pv/Mv of query rows 64b..64b+63 and the five match masks (A, C, G, T, N) of
-// those rows.  Columns run as a skewed wavefront: at step s lane b does column s-b and takes
-// the horizontal delta and the target base of that column from lane b-1 (one DPP wave_shr:1
-// of a packed word).  Lane 0 gets its base from a 64-column chunk of the target that the
-// wave loads coalesced and keeps in a register (v_readlane by the step), and its delta from
-// the top boundary (0 infix, +1 prefix/global) or, for a query of more than 4096 rows, from the
-// boundary row the previous stripe's last lane left: 2 bits per column, in LDS for targets
-// up to PAIR_LDS_COLUMNS, else in a per-wave global scratch row.
+// The passes are edlib_wave.h's: a wave_locate per extension, a global dp_pass at the end, over
+// five symbols (A, C, G, T, N) and with nothing kept but the bottom row.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,14 +19,19 @@
 
 #include "../../include/canu_pair.h"
 #include "capi_common.h"
+#include "edlib_launch.h"
 
 namespace {
 
 using capi::fail;
+using edw::LDS_WORDS;
+using edw::Span;
+using edw::uni;
+using edw::WAVES_PER_BLOCK;
 
 CAPI_SAME_CODES(PAIR);
-constexpr int WAVES_PER_BLOCK = 4;
-constexpr int LDS_WORDS = PAIR_LDS_COLUMNS / 16;      // boundary row of one wave, 2 bits/column
+static_assert(PAIR_STRIPE_ROWS == edw::STRIPE_ROWS && PAIR_LDS_COLUMNS == edw::LDS_COLUMNS,
+              "canu_pair.h names the aligner's stripe and LDS row");
 constexpr int MHAP_SLOP = 500;                         // overlapPair.C:64
 constexpr uint32_t MAX_EVALUE = 4095;                  // AS_MAX_EVALUE, ovOverlap.H:42
 
@@ -52,150 +50,6 @@ struct ReadTable {
   uint32_t first_iid, nreads;
 };
 
-// ------------------------------------------------------------------ read encoding
-
-__global__ void k_encode(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ src_off,
-                         const uint64_t *__restrict__ dst_off, const uint32_t *__restrict__ len,
-                         uint32_t nreads, uint8_t *__restrict__ fwd, uint8_t *__restrict__ rc,
-                         uint32_t *__restrict__ bad) {
-  for (uint32_t r = blockIdx.x; r < nreads; r += gridDim.x) {
-    const uint8_t *s = bases + src_off[r];
-    const uint64_t d = dst_off[r];
-    const uint32_t L = len[r];
-    for (uint32_t i = threadIdx.x; i < L; i += blockDim.x) {
-      const uint8_t ch = s[i];
-      uint8_t c = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : 4;
-      if (c == 4 && ch != 'N') atomicOr(bad, 1u);
-      fwd[d + i] = c;
-      rc[d + (L - 1 - i)] = c < 4 ? (uint8_t)(3 - c) : c;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ the aligner
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ int dpp_from_lower(int v, int lane0) {   // lane l <- v[l-1]
-  return __builtin_amdgcn_update_dpp(lane0, v, 0x138, 0xf, 0xf, false);
-}
-
-struct Seq {                 // a span of an oriented read, read forwards or backwards
-  const uint8_t *p;          // first base of the span
-  int n;
-  int rev;                   // element i is p[n-1-i]
-  __device__ __forceinline__ int at(int i) const { return p[rev ? n - 1 - i : i]; }
-};
-
-struct PassOut {
-  int best, bestcol;         // minimum of the bottom row, the first column attaining it
-  int lastcol;               // last column whose bottom-row score == want (-1: none)
-  int fin;                   // bottom-row score at the last column
-};
-
-// Bottom row of the edit-distance matrix of q (rows) against t (columns); top_hin 0 lets an
-// alignment start at any column (infix), 1 charges every skipped target base (prefix, global).
-// Needs q.n >= 1, t.n >= 1.  Every lane of the wave is in, with the same arguments.
-__device__ PassOut dp_pass(const Seq q, const Seq t, const int top_hin, const int want,
-                           uint32_t *lrow, uint32_t *grow, unsigned long long &steps) {
-  const int lane = threadIdx.x & 63;
-  const int m = q.n, n = t.n;
-  const int nstripes = (m + PAIR_STRIPE_ROWS - 1) / PAIR_STRIPE_ROWS;
-  const bool use_g = n > PAIR_LDS_COLUMNS;
-  int best = INT_MAX, bestcol = -1, lastcol = -1, sc = m;
-  int lb = 0;
-  for (int st = 0; st < nstripes; st++) {
-    const int r0 = st * PAIR_STRIPE_ROWS;
-    const int rows = min(PAIR_STRIPE_ROWS, m - r0);
-    const int nb = (rows + 63) >> 6;
-    const bool last = st == nstripes - 1;
-    lb = nb - 1;
-    // match masks: block c's 64 bases are loaded by the wave and balloted per letter
-    uint64_t pe0 = 0, pe1 = 0, pe2 = 0, pe3 = 0, pe4 = 0;
-    for (int c = 0; c < nb; c++) {
-      const int i = r0 + c * 64 + lane;
-      const int code = i < m ? q.at(i) : 7;
-      const uint64_t b0 = __ballot(code == 0), b1 = __ballot(code == 1),
-                     b2 = __ballot(code == 2), b3 = __ballot(code == 3),
-                     b4 = __ballot(code == 4);
-      if (lane == c) { pe0 = b0; pe1 = b1; pe2 = b2; pe3 = b3; pe4 = b4; }
-    }
-    uint64_t Pv = ~0ull, Mv = 0;
-    const bool trk = last && lane == lb;
-    const int rr = trk ? ((m - 1) & 63) : 63;
-    sc = m;
-    int x = 1;                                  // (hout + 1) | base << 2, handed to lane + 1
-    uint32_t cur = lane < n ? (uint32_t)t.at(lane) : 4u;
-    uint32_t nxt = 64 + lane < n ? (uint32_t)t.at(64 + lane) : 4u;
-    uint32_t hw = 0, acc = 0;
-    const int nsteps = n + nb - 1;
-    steps += (unsigned long long)nsteps;
-    for (int s = 0; s < nsteps; s++) {
-      if ((s & 63) == 0 && s > 0) {
-        cur = nxt;
-        const int c = s + 64 + lane;
-        nxt = c < n ? (uint32_t)t.at(c) : 4u;
-      }
-      const int base0 = __builtin_amdgcn_readlane((int)cur, s & 63);
-      int hin0 = top_hin;
-      if (st > 0) {
-        if ((s & 15) == 0 && s < n) hw = use_g ? grow[s >> 4] : lrow[s >> 4];
-        hin0 = (int)((hw >> (2 * (s & 15))) & 3u) - 1;
-      }
-      const int xin = dpp_from_lower(x, (hin0 + 1) | (base0 << 2));
-      const int j = s - lane;
-      const bool act = lane < nb && j >= 0 && j < n;
-      int d = 0;
-      if (act) {
-        const int hin = (xin & 3) - 1;
-        const int b = xin >> 2;
-        // the letter's match mask by bit selects (a chain of ?: compiles to branches)
-        const uint64_t s0 = 0 - (uint64_t)(b & 1), s1 = 0 - (uint64_t)((b >> 1) & 1),
-                       s2 = 0 - (uint64_t)(b >> 2);
-        const uint64_t e01 = (pe0 & ~s0) | (pe1 & s0), e23 = (pe2 & ~s0) | (pe3 & s0);
-        const uint64_t e03 = (e01 & ~s1) | (e23 & s1);
-        uint64_t Eq = (e03 & ~s2) | (pe4 & s2);
-        const uint64_t neg = hin < 0 ? 1ull : 0ull, pos = hin > 0 ? 1ull : 0ull;
-        const uint64_t Xv = Eq | Mv;
-        Eq |= neg;
-        const uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-        uint64_t Ph = Mv | ~(Xh | Pv);
-        uint64_t Mh = Pv & Xh;
-        d = (int)((Ph >> rr) & 1) - (int)((Mh >> rr) & 1);
-        Ph = (Ph << 1) | pos;
-        Mh = (Mh << 1) | neg;
-        Pv = Mh | ~(Xv | Ph);
-        Mv = Ph & Xv;
-        sc += d;
-        if (trk) {
-          if (sc < best) { best = sc; bestcol = j; }
-          if (sc == want) lastcol = j;
-        }
-        if (!last && lane == lb) {              // lane 63: the next stripe's top boundary
-          acc |= (uint32_t)(d + 1) << (2 * (j & 15));
-          if ((j & 15) == 15 || j == n - 1) {
-            if (use_g) grow[j >> 4] = acc; else lrow[j >> 4] = acc;
-            acc = 0;
-          }
-        }
-      }
-      x = (d + 1) | (xin & ~3);
-    }
-    if (!last) __threadfence();                 // lane 63's row is read by every lane next
-  }
-  PassOut o;
-  o.best = __shfl(best, lb);
-  o.bestcol = __shfl(bestcol, lb);
-  o.lastcol = __shfl(lastcol, lb);
-  o.fin = __shfl(sc, lb);
-  return o;
-}
-
-struct Oriented {            // an oriented read
-  const uint8_t *p;
-  int len;
-};
-
 struct WaveCtx {
   uint32_t *lrow, *grow;
   double erate;
@@ -210,32 +64,22 @@ __device__ __forceinline__ int max_edit(int a, int b, double erate) {
 
 // extendAlignment (overlapPair.C:255-304): Q[qb,qe) is the query, T[tb,te) widened by slop
 // the target; on success tb/te move to the alignment found.
-__device__ bool extend_alignment(WaveCtx &w, const Oriented Q, int qb, int qe, const Oriented T,
-                                 int &tb, int &te, int slop, int &edit_dist, int &align_len) {
+__device__ bool extend_alignment(WaveCtx &w, const Span Q, int qb, int qe, const Span T, int &tb,
+                                 int &te, int slop, int &edit_dist, int &align_len) {
   const int tbx = max(0, tb - slop);
-  const int tex = min(T.len, te + slop);
+  const int tex = min(T.n, te + slop);
   const int m = qe - qb, n = tex - tbx;
   if (m <= 0 || n <= 0) return false;           // cannot happen with min_overlap_length >= 1
-  const int k = max_edit(m, n, w.erate);
-  const Seq q{Q.p + qb, m, 0};
-  const Seq t{T.p + tbx, n, 0};
-  PassOut f = dp_pass(q, t, 0, INT_MIN, w.lrow, w.grow, w.steps);
-  w.cells += (unsigned long long)m * n;
-  w.passes++;
-  const int best = uni(f.best), end = uni(f.bestcol);
-  if (best > k) return false;
-  // the start: prefix pass of the reversed query over the reversed target[0..end]; the
-  // last column still at `best` is the longest alignment (edlib.C:216-236)
-  const Seq qr{Q.p + qb, m, 1};
-  const Seq tr{T.p + tbx, end + 1, 1};
-  PassOut r = dp_pass(qr, tr, 1, best, w.lrow, w.grow, w.steps);
-  w.cells += (unsigned long long)m * (end + 1);
-  w.passes++;
-  const int start = end - uni(r.lastcol);
-  tb = tbx + start;
-  te = tbx + end + 1;
-  edit_dist = best;
-  align_len = (m + (te - tb) + best) / 2;
+  const edw::Located L = edw::wave_locate<5>(Q.sub(qb, m), T.sub(tbx, n), max_edit(m, n, w.erate),
+                                             true, w.lrow, w.grow);
+  w.cells += L.cells;
+  w.steps += L.steps;
+  w.passes += L.passes;
+  if (!L.ok) return false;
+  tb = tbx + L.start;
+  te = tbx + L.end + 1;
+  edit_dist = L.dist;
+  align_len = (m + (te - tb) + L.dist) / 2;
   return true;
 }
 
@@ -282,8 +126,8 @@ void k_pair(const ReadTable R, const ovl_record *__restrict__ in, const uint32_t
     }
     const uint32_t ra = a_iid - R.first_iid, rb = b_iid - R.first_iid;   // checked on the host
     const int alen = uni((int)R.len[ra]), blen = uni((int)R.len[rb]);
-    const Oriented A{R.fwd + R.off[ra], alen};
-    const Oriented B{(flipped ? R.rc : R.fwd) + R.off[rb], blen};
+    const Span A{R.fwd + R.off[ra], alen};
+    const Span B{(flipped ? R.rc : R.fwd) + R.off[rb], blen};
 
     int abgn = ahg5, aend = alen - ahg3, bbgn = bhg5, bend = blen - bhg3;
     int align_len = 1, edit_dist = INT_MAX;
@@ -332,10 +176,10 @@ void k_pair(const ReadTable R, const ovl_record *__restrict__ in, const uint32_t
         const int m = fe - fa, n = fbe - fb;
         if (m > 0 && n > 0) {
           const int k = max_edit(m, n, erate);
-          const Seq q{A.p + fa, m, 0};
-          const Seq t{B.p + fb, n, 0};
-          PassOut g = dp_pass(q, t, 1, INT_MIN, w.lrow, w.grow, w.steps);
+          const edw::PassOut g = edw::dp_pass<5>(A.sub(fa, m).fwd(), B.sub(fb, n).fwd(), 1, INT_MIN,
+                                                 w.lrow, w.grow, edw::NoKeep{});
           w.cells += (unsigned long long)m * n;
+          w.steps += g.steps;
           w.passes++;
           const int ed = uni(g.fin);
           if (ed <= k) { edit_dist = ed; align_len = (m + n + ed) / 2; }
@@ -410,12 +254,7 @@ void k_pair(const ReadTable R, const ovl_record *__restrict__ in, const uint32_t
 
 struct pair_ctx : capi::Device {
   pair_params P{};
-  uint32_t first_iid = 0, nreads = 0;
-  std::vector<uint32_t> len;
-  uint32_t max_len = 0;
-  DevBuf<uint8_t> d_fwd, d_rc;
-  DevBuf<uint64_t> d_off;
-  DevBuf<uint32_t> d_len;
+  edw::Strands R;
   pair_stats S{};
 };
 
@@ -429,13 +268,6 @@ int check_params(const pair_params *p) {
     return fail(PAIR_ERR_BAD_PARAM, "min_overlap_length 0 is not supported: the reference "
                                     "aligns empty spans there; use 1 or more");
   return PAIR_OK;
-}
-
-void free_reads(pair_ctx *c) {
-  c->d_fwd.release(); c->d_rc.release(); c->d_off.release(); c->d_len.release();
-  c->nreads = 0;
-  c->len.clear();
-  c->max_len = 0;
 }
 
 }  // namespace
@@ -475,45 +307,7 @@ int pair_load_reads_device(pair_ctx *c, uint32_t first_iid, uint32_t nreads,
   if (!c) return fail(PAIR_ERR_BAD_PARAM, "null context");
   if (int rc = capi::check_device_reads(first_iid, nreads, d_bases, d_offsets, h_lengths)) return rc;
   HIP_TRY(hipSetDevice(c->device));
-  free_reads(c);
-  std::vector<uint64_t> off(nreads);
-  uint64_t total = 0;
-  uint32_t mx = 0;
-  for (uint32_t i = 0; i < nreads; i++) {
-    if (h_lengths[i] > (1u << 21) - 1)
-      return fail(PAIR_ERR_BAD_INPUT, "read %u is %u bases, beyond AS_MAX_READLEN", first_iid + i,
-                  h_lengths[i]);
-    off[i] = total;
-    total += h_lengths[i];
-    mx = std::max(mx, h_lengths[i]);
-  }
-  DevBuf<uint32_t> bad;
-  HIP_TRY(bad.alloc(1));
-  HIP_TRY(c->d_fwd.alloc(total));
-  HIP_TRY(c->d_rc.alloc(total));
-  HIP_TRY(c->d_off.alloc(nreads));
-  HIP_TRY(c->d_len.alloc(nreads));
-  HIP_TRY(hipMemsetAsync(bad.p, 0, 4, c->stream));
-  uint32_t h_bad = 0;
-  if (nreads) {
-    HIP_TRY(hipMemcpyAsync(c->d_off.p, off.data(), nreads * 8ull, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_len.p, h_lengths, nreads * 4ull, hipMemcpyHostToDevice, c->stream));
-    const uint32_t grid = std::min<uint32_t>(nreads, 4096);
-    hipLaunchKernelGGL(k_encode, dim3(grid), dim3(256), 0, c->stream, d_bases, d_offsets, c->d_off.p,
-                       c->d_len.p, nreads, c->d_fwd.p, c->d_rc.p, bad.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h_bad, bad.p, 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  if (h_bad) {
-    free_reads(c);
-    return fail(PAIR_ERR_BAD_INPUT, "a read holds a byte outside ACGTN");
-  }
-  c->first_iid = first_iid;
-  c->nreads = nreads;
-  c->len.assign(h_lengths, h_lengths + nreads);
-  c->max_len = mx;
-  return PAIR_OK;
+  return edw::load_strands(c->R, c->stream, true, first_iid, nreads, d_bases, d_offsets, h_lengths);
 }
 
 int pair_load_reads(pair_ctx *c, uint32_t first_iid, uint32_t nreads, const uint8_t *bases,
@@ -541,11 +335,11 @@ int pair_realign(pair_ctx *c, const ovl_record *in, uint64_t n, ovl_record *out)
     uint64_t a5 = in[i].dat[0] & HM, a3 = (in[i].dat[0] >> 21) & HM;
     uint64_t b5 = in[i].dat[1] & HM, b3 = (in[i].dat[1] >> 21) & HM;
     if (c->P.invert) { std::swap(a, b); std::swap(a5, b5); std::swap(a3, b3); }
-    if (a < c->first_iid || a - c->first_iid >= c->nreads || b < c->first_iid ||
-        b - c->first_iid >= c->nreads)
+    if (a < c->R.first_iid || a - c->R.first_iid >= c->R.nreads || b < c->R.first_iid ||
+        b - c->R.first_iid >= c->R.nreads)
       return fail(PAIR_ERR_BAD_INPUT, "overlap %llu names read %u or %u, not loaded",
                   (unsigned long long)i, a, b);
-    const uint64_t al = c->len[a - c->first_iid], bl = c->len[b - c->first_iid];
+    const uint64_t al = c->R.len[a - c->R.first_iid], bl = c->R.len[b - c->R.first_iid];
     if (a5 + a3 > al || b5 + b3 > bl)
       return fail(PAIR_ERR_BAD_INPUT, "overlap %llu: hangs beyond its reads (%u: %llu+%llu of "
                   "%llu, %u: %llu+%llu of %llu)", (unsigned long long)i, a,
@@ -564,7 +358,7 @@ int pair_realign(pair_ctx *c, const ovl_record *in, uint64_t n, ovl_record *out)
   const uint64_t max_blocks = (uint64_t)c->n_cu * 8;   // 8 waves per SIMD
   const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
                                                        max_blocks);
-  const uint64_t scratch_words = need_scratch ? ((uint64_t)c->max_len + 15) / 16 : 0;
+  const uint64_t scratch_words = need_scratch ? edw::grow_words(c->R.max_len) : 0;
 
   DevBuf<ovl_record> d_in, d_out;
   DevBuf<uint32_t> d_order, d_flags, d_passes, d_scratch;
@@ -581,7 +375,7 @@ int pair_realign(pair_ctx *c, const ovl_record *in, uint64_t n, ovl_record *out)
   HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), n * 4, hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemsetAsync(d_flags.p, 0, n * 4, c->stream));
 
-  ReadTable R{c->d_fwd.p, c->d_rc.p, c->d_off.p, c->d_len.p, c->first_iid, c->nreads};
+  ReadTable R{c->R.fwd.p, c->R.rc.p, c->R.d_off.p, c->R.d_len.p, c->R.first_iid, c->R.nreads};
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0));
   HIP_TRY(hipEventCreate(&e1));
